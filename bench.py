@@ -5,18 +5,23 @@ A "step" is one pass of the whole hot path (IQ -> packet list) over one batch of
 already resident in HBM when the timed region starts.
 
   python bench.py [--gpus N --steps K --warmup W] [--workload 64msps|2msps|20msps] [--lambda L] [--replicas]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (plus DIR/<name>.npy with --dump-outputs:
+the packets of the last timed step, one float32 / float64 array per field).  Everything else -- parity against
+the oracle, the CPU baselines, the extra legs named below -- runs only with --full.
 
 N = 1  workload "64msps" (BASELINE.json configs[2]: synthetic 64 Msps IQ, Poisson-injected Mode-S bursts in
        AWGN).  The timed loop rotates over three distinct 512 MB batches (the 256 MiB Infinity Cache cannot
-       serve them), the packets of the last batch are compared with the oracle (`parity`).  The default burst
-       rate (20 000 /s, 87 % airtime) is a stress density; `realistic_density` repeats the measurement at
-       2 000 bursts/s in the same run.
+       serve them), with --full the packets of the last batch are compared with the oracle (`parity`).  The
+       default burst rate (20 000 /s, 87 % airtime) is a stress density; with --full `realistic_density`
+       repeats the measurement at 2 000 bursts/s in the same run.
 N > 1  configs[3]: one 64 Msps stream time-sharded over the N GPUs, one process per GPU (torch.distributed
        over RCCL): a step is the next N seconds of ONE continuing stream, one second per GPU; every rank's tail
        travels to the next rank as a point-to-point send / receive (KB scale), every rank scans its chunk, the
        scan's exit tables are all-gathered, every rank slices its own hits; scan position and sample count
        cross the steps.  Per-GPU work is fixed as N grows ("weak").  `python bench.py --gpus N` launches the
-       N ranks itself when it is not already running under torch.distributed.run.  `parity` for N > 1: a short
+       N ranks itself when it is not already running under torch.distributed.run.  `parity` for N > 1 (--full): a short
        stream through the same N-rank receiver in two steps against the oracle over the whole stream, plus
        rank 0's full-size packets against the oracle over its samples.
        --replicas: configs[4] instead -- N independent receivers (20 Msps each unless --workload says
@@ -24,8 +29,8 @@ N > 1  configs[3]: one 64 Msps stream time-sharded over the N GPUs, one process 
        against the oracle.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the front end, the only kernel that
-touches every sample): algorithmic bytes = 8 B per complex sample.  `cpu_baseline` is the oracle (a scalar C
-port of the reference path) timed on this host.
+touches every sample): algorithmic bytes = 8 B per complex sample.  `cpu_baseline` (--full) is the oracle (a
+scalar C port of the reference path) timed on this host.
 
 --emu (tests only): the same orchestration on CPU -- gloo, the CPU-fiber build of the kernels (tests/emu),
 tiny sizes.  The line it prints carries "emulated": true and is not a measurement.
@@ -59,6 +64,27 @@ REALISTIC_LAMBDA = 2000.0  # bursts per second of the second density
 def ctx_messages(ctx, packets):
     """Message texts of a packet array as the library formats them (first message: 6 significant digits)."""
     return ctx.lib.format_messages(packets, True)          # (am_format_messages: one call per batch)
+
+
+def dump_outputs(folder, outputs, limit=63 << 20):
+    """--dump-outputs: `outputs` maps a name to the packet array (PACKET_DTYPE) the timed path returned in its last step.  Every
+    field but the reserved bytes goes to folder/<name>_<field>.npy, float32 where that is exact (bytes, the f32 reference level),
+    float64 otherwise (crc, sample counts, time stamps).  Beyond `limit` bytes in all, a fixed seeded sample of the packets, in
+    order, stands for each array."""
+    os.makedirs(folder, exist_ok=True)
+
+    def as_float(col):
+        return col.astype(np.float32 if col.dtype.itemsize == 1 or col.dtype == np.float32 else np.float64)
+    dtype = next(iter(outputs.values())).dtype
+    fields = [f for f in dtype.names if not f.startswith("reserved")]
+    row_bytes = sum(as_float(np.zeros(1, dtype)[f]).nbytes for f in fields)
+    rows = sum(len(a) for a in outputs.values())
+    for name, a in outputs.items():
+        if rows * row_bytes > limit:
+            keep = len(a) * (limit // row_bytes) // rows
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        for f in fields:
+            np.save(os.path.join(folder, "%s_%s.npy" % (name, f)), as_float(a[f]))
 
 
 def free_port():
@@ -106,7 +132,16 @@ def parse_args():
                                                            "(am_process_multi): N = 1, value counts all K streams")
     ap.add_argument("--replicas", action="store_true", help="N independent receivers, one per GPU (configs[4])")
     ap.add_argument("--emu", action="store_true", help="tests only: CPU emulation of the kernels, gloo")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: parity against the oracle, the CPU baselines and the extra legs "
+                         "(--no-parity / --no-cpu-baseline / --no-extra / --no-pipelined trim them); without it a run sets up, warms "
+                         "up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the packets of the last timed step as DIR/<name>.npy, one float32 / float64 array per packet field")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -242,19 +277,22 @@ def main():
         dt, k_last, pk, fe_ms = timed(args.steps, ctxs, inflight, d_batches)
         last_batch = (k_last % nb) if k_last is not None else 0
         npk_steps = sum(per_batch[k % nb] for k in range(args.steps))
+        outputs = {"stream%d_packets" % j: g for j, g in enumerate(pk)} if K > 1 else {"packets": pk}
         if K > 1:
-            # parity: EVERY stream's packets against the oracle over that stream alone
-            parity_k = None
-            if not args.no_parity:
-                import oracle
-                parity_k = all(g.tobytes() == oracle.demod(x, rate, 7.0, True).tobytes() for g, x in zip(pk, k_hosts[0]))
-            one = ctx.process_iq_device(d_batches[0].data_ptr(), n, flush=True)      # (stream 0 lies at offset 0)
-            extra["k_streams"] = {"streams_per_scan": K, "samples_per_stream": n, "samples_scanned_per_step": int(k_total),
-                                  "parity_every_stream": parity_k,
-                                  "same_as_single_stream_call": bool(one.tobytes() == pk[0].tobytes()),
-                                  "packets_per_stream": [int(len(g)) for g in pk]}
+            extra["k_streams"] = {"streams_per_scan": K, "samples_per_stream": n, "samples_scanned_per_step": int(k_total)}
+            if args.full:
+                # parity: EVERY stream's packets against the oracle over that stream alone
+                parity_k = None
+                if not args.no_parity:
+                    import oracle
+                    parity_k = all(g.tobytes() == oracle.demod(x, rate, 7.0, True).tobytes() for g, x in zip(pk, k_hosts[0]))
+                one = ctx.process_iq_device(d_batches[0].data_ptr(), n, flush=True)      # (stream 0 lies at offset 0)
+                extra["k_streams"].update({"parity_every_stream": parity_k,
+                                           "same_as_single_stream_call": bool(one.tobytes() == pk[0].tobytes())})
+            extra["k_streams"]["packets_per_stream"] = [int(len(g)) for g in pk]
             pk = pk[0]
-        if mode == "single" and K == 1 and not args.no_extra and workload != "64msps" and args.steps >= 3:
+        extras = args.full and not args.no_extra
+        if mode == "single" and K == 1 and extras and workload != "64msps" and args.steps >= 3:
             # 2 / 20 Msps: one second of ONE receiver is a small job for the chip (the scan's launches are most of the step); eight
             # receivers' seconds in one scan (am_process_multi: K whole streams in one buffer, zeros between them)
             # ONE receiver as configs[1] / [4] have it (VERDICT r5 #6a): (a) multi-second scans -- eight seconds of the one stream per
@@ -386,7 +424,7 @@ def main():
             kp.close()
             del kd, kh
             run_steps(2, [ctx], 1, d_batches)
-        if mode == "single" and K == 1 and not args.no_extra and not args.no_pipelined and inflight == 1 and args.steps >= 3:
+        if mode == "single" and K == 1 and extras and not args.no_pipelined and inflight == 1 and args.steps >= 3:
             # the same batches with four in flight from ONE host thread (am_pipe: four contexts behind one handle, submit /
             # collect): the launch-latency-bound tail of one batch overlaps the streaming kernel of the next.  Timed over
             # 24 batches including the filling and the draining of the pipe (depth 3: ~4 % less, 5 and more: less again --
@@ -421,7 +459,7 @@ def main():
                                   "same_packet_counts": counts3 == [per_batch[k % nb] for k in range(PIPE_BATCHES)],
                                   "same_packets_last_batch": bool(np.array_equal(last3, want_last))}
             pipe.close()
-        if mode == "single" and K == 1 and not args.no_extra and not args.no_pipelined and inflight == 1 and args.stream_seconds > 0 \
+        if mode == "single" and K == 1 and extras and not args.no_pipelined and inflight == 1 and args.stream_seconds > 0 \
                 and args.steps >= 3:
             # ONE continuing stream with four of its consecutive chunks in flight (am_spipe): the reference block is a
             # streaming block (lib/preamble_impl.cc:139-246) -- chunk k + 1's scan is enqueued before chunk k resolves, the scan
@@ -474,7 +512,7 @@ def main():
             sp.close()
             del sbufs
             run_steps(2, [ctx], 1, d_batches)
-        if mode == "single" and K == 1 and not args.no_extra and lam != REALISTIC_LAMBDA:
+        if mode == "single" and K == 1 and extras and lam != REALISTIC_LAMBDA:
             iq_r = synth.synth_capture(rate, n, REALISTIC_LAMBDA, seed + 7)[0]
             d_r = [torch.from_numpy(iq_r.view(np.float32)).to(dev)]
             run_steps(3, [ctx], 1, d_r)
@@ -489,7 +527,7 @@ def main():
                 import oracle
                 extra["realistic_density"]["parity"] = bool(np.array_equal(pkr, oracle.demod(iq_r, rate, 7.0, True)))
             run_steps(2, [ctx], 1, d_batches)          # back to the main density (capacity estimate of the context)
-        if mode == "single" and K == 1 and not args.no_extra and args.sustained_steps > 0 and not args.emu:
+        if mode == "single" and K == 1 and extras and args.sustained_steps > 0 and not args.emu:
             # the timed loop again, long enough (>= 0.5 s of device work) for a sampler of GPU activity to see the device busy: the same
             # rotating batches, the same call, nothing skipped; the packets of its last step are checked against the first pass's count
             run_steps(2, [ctx], 1, d_batches)
@@ -499,7 +537,7 @@ def main():
                                   "ms_per_step": dts / args.sustained_steps * 1e3, "kernel_ms": fe_s,
                                   "roofline_frac": (8.0 * n / (fe_s * 1e-3) / 1e9 / HBM_PEAK_GBS) if fe_s > 0 else 0.0,
                                   "same_packet_count_as_timed_loop": bool(len(pks) == per_batch[ks_last % nb])}
-        if mode == "single" and K == 1 and not args.no_extra:
+        if mode == "single" and K == 1 and extras:
             # the same step with the batch in HOST memory (a file source): pinned staging, two buffers in flight -- the PCIe copy
             # of batch k+1 overlaps the scan of batch k (am_uploader_*, what modes_rx does).  PCIe bound; reported separately,
             # never as `value`.  `pageable` = one synchronous host-to-device copy inside am_process_iq (round 2's figure).
@@ -537,7 +575,7 @@ def main():
             run_steps(2, [ctx], 1, d_batches)
         iq_check = host_batches[last_batch]
         parity = None
-        if mode == "replicas":
+        if mode == "replicas" and args.full:
             import oracle
             ok = bool(np.array_equal(pk, oracle.demod(iq_check, rate, 7.0, True)))
             if K > 1:
@@ -642,56 +680,59 @@ def main():
                                           "through_the_process_group": bool(world > 1 or rx.force),
                                           "tail_by": ("all_gather (the backend refused a send to itself)" if rx.tail_by_gather else
                                                       "batch_isend_irecv") if (world > 1 or rx.force) else "device copy (one rank, no group)"}
-        # parity, part 1: a short stream through the same N-rank receiver IN TWO STEPS against the oracle over the WHOLE stream
-        import oracle
-        ns = max(4 * rx.halo, 30000 * spc)
-        whole = synth.synth_capture(rate, 2 * world * ns, lam, 4242)[0]
-        mine = []
-        if in_flight:
-            rx_s = PipelinedShardedReceiver([new_ctx(), new_ctx()], rank, world, ns, device=dev, force_collectives=forced)
-            for k in range(2):
-                a = (k * world + rank) * ns
-                rx_s.chunk.copy_(torch.from_numpy(whole[a:a + ns].copy().view(np.float32)))
-                rx_s.submit(flush=(k == 1))
-            mine = [rx_s.collect(), rx_s.collect()]
-        else:
-            rx_s = ShardedReceiver(new_ctx(), rank, world, ns, device=dev, force_collectives=forced)
-            for k in range(2):
-                a = (k * world + rank) * ns
-                rx_s.chunk.copy_(torch.from_numpy(whole[a:a + ns].copy().view(np.float32)))
-                mine.append(rx_s.step(flush=(k == 1)))
-        if world > 1:
-            parts = [None] * world
-            dist.all_gather_object(parts, [m.tobytes() for m in mine])
-            got = np.concatenate([np.frombuffer(parts[r][k], _capi.PACKET_DTYPE) for k in range(2) for r in range(world)])
-        else:
-            got = np.concatenate(mine)
-        parity_small = bool(np.array_equal(got, oracle.demod(whole, rate, 7.0, True)))
-        # part 2: the full-size chunk as a finite stream of its own (flush): rank 0's packets against the oracle over its samples
-        if in_flight:
-            # (the stream the timed region fed never ended: a fresh receiver for the finite one)
-            rx.close()
-            rx = PipelinedShardedReceiver(ctxs, rank, world, n, device=dev, force_collectives=forced)
-            for c_ in ctxs:
-                c_.reset()
-            rx.chunk.copy_(torch.from_numpy(iq.view(np.float32)))
-        else:
-            rx.reset()
-            rx._select(0)                                     # (the buffer that holds `iq`)
-        pk0 = rx.step(flush=True)
-        parity_rank0 = None
-        if rank == 0:
-            want = oracle.demod(iq, rate, 7.0, True)
-            if world > 1:
-                # rank 0 decides the positions its own samples let it decide ([0, n - H)); the oracle, whose stream ends
-                # after them, may add hits beyond
-                keep, rest = want[:len(pk0)], want[len(pk0):]
-                parity_rank0 = bool(np.array_equal(pk0, keep) and (len(rest) == 0 or int(rest["sample"][0]) >= n - rx.hold))
+        outputs = {"packets": pk}
+        parity = None
+        if args.full:
+            # parity, part 1: a short stream through the same N-rank receiver IN TWO STEPS against the oracle over the WHOLE stream
+            import oracle
+            ns = max(4 * rx.halo, 30000 * spc)
+            whole = synth.synth_capture(rate, 2 * world * ns, lam, 4242)[0]
+            mine = []
+            if in_flight:
+                rx_s = PipelinedShardedReceiver([new_ctx(), new_ctx()], rank, world, ns, device=dev, force_collectives=forced)
+                for k in range(2):
+                    a = (k * world + rank) * ns
+                    rx_s.chunk.copy_(torch.from_numpy(whole[a:a + ns].copy().view(np.float32)))
+                    rx_s.submit(flush=(k == 1))
+                mine = [rx_s.collect(), rx_s.collect()]
             else:
-                parity_rank0 = bool(np.array_equal(pk0, want))
-        parity = parity_small if parity_rank0 is None else bool(parity_small and parity_rank0)
-        extra["parity_detail"] = {"short_stream_two_steps_all_ranks": parity_small, "rank0_full_size": parity_rank0,
-                                  "short_stream_samples_per_rank_per_step": ns}
+                rx_s = ShardedReceiver(new_ctx(), rank, world, ns, device=dev, force_collectives=forced)
+                for k in range(2):
+                    a = (k * world + rank) * ns
+                    rx_s.chunk.copy_(torch.from_numpy(whole[a:a + ns].copy().view(np.float32)))
+                    mine.append(rx_s.step(flush=(k == 1)))
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, [m.tobytes() for m in mine])
+                got = np.concatenate([np.frombuffer(parts[r][k], _capi.PACKET_DTYPE) for k in range(2) for r in range(world)])
+            else:
+                got = np.concatenate(mine)
+            parity_small = bool(np.array_equal(got, oracle.demod(whole, rate, 7.0, True)))
+            # part 2: the full-size chunk as a finite stream of its own (flush): rank 0's packets against the oracle over its samples
+            if in_flight:
+                # (the stream the timed region fed never ended: a fresh receiver for the finite one)
+                rx.close()
+                rx = PipelinedShardedReceiver(ctxs, rank, world, n, device=dev, force_collectives=forced)
+                for c_ in ctxs:
+                    c_.reset()
+                rx.chunk.copy_(torch.from_numpy(iq.view(np.float32)))
+            else:
+                rx.reset()
+                rx._select(0)                                     # (the buffer that holds `iq`)
+            pk0 = rx.step(flush=True)
+            parity_rank0 = None
+            if rank == 0:
+                want = oracle.demod(iq, rate, 7.0, True)
+                if world > 1:
+                    # rank 0 decides the positions its own samples let it decide ([0, n - H)); the oracle, whose stream ends
+                    # after them, may add hits beyond
+                    keep, rest = want[:len(pk0)], want[len(pk0):]
+                    parity_rank0 = bool(np.array_equal(pk0, keep) and (len(rest) == 0 or int(rest["sample"][0]) >= n - rx.hold))
+                else:
+                    parity_rank0 = bool(np.array_equal(pk0, want))
+            parity = parity_small if parity_rank0 is None else bool(parity_small and parity_rank0)
+            extra["parity_detail"] = {"short_stream_two_steps_all_ranks": parity_small, "rank0_full_size": parity_rank0,
+                                      "short_stream_samples_per_rank_per_step": ns}
         iq_check = iq
 
     # ------------------------------------------------------------------------------------------------------------
@@ -727,6 +768,13 @@ def main():
         one = torch.ones(1, dtype=torch.float64, device=dev)
         dist.all_reduce(one, op=dist.ReduceOp.SUM)               # (through the data-path backend itself: RCCL on the GPU box)
         ranks_seen = int(round(float(one[0].item())))
+    if args.dump_outputs:
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, {k: v.tobytes() for k, v in outputs.items()})
+            outputs = {"rank%d_%s" % (r, k): np.frombuffer(b, _capi.PACKET_DTYPE) for r, p in enumerate(parts) for k, b in p.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         total_samples = world * K * n * args.steps
         value = total_samples / dt
@@ -817,8 +865,8 @@ def main():
             res["emulated"] = True
         if parity is not None:
             res["parity"] = parity
-        if not args.no_parity and (mode == "single" or not args.no_cpu_baseline):
-            # every line carries its parity bit (the checker runs outside the timed regions); the same pass of the oracle is
+        if args.full and not args.no_parity and (mode == "single" or not args.no_cpu_baseline):
+            # with --full every line carries its parity bit (the checker runs outside the timed regions); the same pass of the oracle is
             # the single-core CPU baseline unless --no-cpu-baseline
             import oracle
             t1 = time.perf_counter()
@@ -834,7 +882,7 @@ def main():
                                                  "(scalar C, gcc -O3, 1 thread), %.2f s" % (n, cpu_dt),
                                        "host_cores_available": os.cpu_count()}
                 res["speedup_vs_cpu_baseline"] = value / (n / cpu_dt)
-        if mode == "single" and K == 1 and not args.no_cpu_baseline and not args.emu:
+        if args.full and mode == "single" and K == 1 and not args.no_cpu_baseline and not args.emu:
             import oracle
             # the same port on every host core: the batch cut into one time chunk per thread (each with the
             # look-ahead a chunk needs), timed only -- SURVEY 8(d) asks for both figures

@@ -6,18 +6,20 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import conftest
 
 
-def run_bench(*extra):
+def run_bench(*extra, full=True):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     env.pop("LOCAL_RANK", None)
     out = subprocess.run([sys.executable, os.path.join(conftest.ROOT, "bench.py"), "--emu", "--steps", "2", "--warmup", "1",
-                          "--no-extra"] + list(extra), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                          "--no-extra"] + (["--full"] if full else []) + list(extra), env=env, stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout.decode()[-2000:]
@@ -29,6 +31,28 @@ def test_single_gpu_line(emu_lib):
     assert d["emulated"] and d["n_gpus"] == 1 and d["parity"] is True
     assert d["config"]["distinct_batches"] == 2 and len(d["config"]["packets_per_batch"]) == 2
     assert d["value"] > 0 and d["roofline"]["bound"] == "hbm" and "cpu_baseline" in d
+
+
+def test_plain_line_and_dumped_outputs(emu_lib, oracle_mod, tmp_path):
+    """Without --full the line carries the headline figure and nothing that needs the oracle; --dump-outputs writes the packets
+    of the last timed step field by field in float32 / float64, the same files again on a second run with the same arguments."""
+    import synth
+    dumps = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        d = run_bench("--workload", "20msps", "--seconds", "0.01", "--batches", "2", "--dump-outputs", str(out), full=False)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "samples/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert "parity" not in d and "cpu_baseline" not in d
+        dumps.append({f: np.load(str(out / f)) for f in os.listdir(str(out))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(a[f].dtype in (np.float32, np.float64) and np.array_equal(a[f], b[f]) for f in a)
+    # the last of the two timed steps scanned the second batch: its packets, as the oracle finds them
+    rate, _, lam, seed = synth.CONFIGS["20msps"]
+    want = oracle_mod.demod(synth.synth_capture(rate, 200000, lam, seed + 100)[0], rate, 7.0, True)
+    assert len(want) > 0 and len(a["packets_sample.npy"]) == len(want) == d["config"]["packets_per_batch"][1]
+    for f in ("sample", "crc", "ref", "data", "frac"):
+        assert np.array_equal(a["packets_%s.npy" % f], want[f].astype(a["packets_%s.npy" % f].dtype)), f
 
 
 def test_gpus_2_launches_two_ranks_time_sharded(emu_lib):

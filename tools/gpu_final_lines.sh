@@ -4,10 +4,10 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/final; rm -rf $OUT; mkdir -p $OUT
 timeout 600 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $OUT/tests_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1
-timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout 200 python bench.py --workload 20msps --no-cpu-baseline --no-extra > $OUT/bench_20msps.json 2>/dev/null
-timeout 200 python bench.py --workload 2msps --no-cpu-baseline --no-extra > $OUT/bench_2msps.json 2>/dev/null
-timeout 200 python bench.py --force-sharded --no-cpu-baseline --no-extra > $OUT/bench_force_sharded.json 2>/dev/null
+timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout 200 python bench.py --full --workload 20msps --no-cpu-baseline --no-extra > $OUT/bench_20msps.json 2>/dev/null
+timeout 200 python bench.py --full --workload 2msps --no-cpu-baseline --no-extra > $OUT/bench_2msps.json 2>/dev/null
+timeout 200 python bench.py --full --force-sharded --no-cpu-baseline --no-extra > $OUT/bench_force_sharded.json 2>/dev/null
 cat $OUT/tests_gpu.txt; tail -2 $OUT/smoke.txt
 python - <<'PY'
 import json

@@ -3,14 +3,14 @@
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/final2; rm -rf $OUT; mkdir -p $OUT
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1
-timeout 200 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 STEPS=10 timeout 200 bash tools/gpu_prof.sh > $OUT/summary.txt 2>&1
 cp gpurun_out/prof_stats/bench_kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null
 cp gpurun_out/bench_prof.json $OUT/bench_under_rocprof.json 2>/dev/null
 AIRMODES_HIP_LIB=$PWD/build/var/lib_fe3prof.so timeout 60 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-parity 2>&1 >/dev/null | grep "^fe3" | tail -32 > $OUT/fe3_timeline.txt 2>&1
 timeout 100 python bench.py --steps 2000 --warmup 20 --no-cpu-baseline --no-extra --no-parity > $OUT/bench_2000_steps.json 2>/dev/null
-timeout 150 python bench.py --workload 20msps --no-cpu-baseline > $OUT/bench_20msps.json 2>/dev/null
-timeout 150 python bench.py --workload 2msps --no-cpu-baseline > $OUT/bench_2msps.json 2>/dev/null
+timeout 150 python bench.py --full --workload 20msps --no-cpu-baseline > $OUT/bench_20msps.json 2>/dev/null
+timeout 150 python bench.py --full --workload 2msps --no-cpu-baseline > $OUT/bench_2msps.json 2>/dev/null
 tail -2 $OUT/smoke.txt
 python - <<'PY'
 import json

@@ -4,11 +4,11 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/kstreams; rm -rf $OUT; mkdir -p $OUT
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $OUT/tests_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1
-timeout 300 python bench.py --no-cpu-baseline --no-extra > $OUT/bench_64msps.json 2> $OUT/bench.err
+timeout 300 python bench.py --full --no-cpu-baseline --no-extra > $OUT/bench_64msps.json 2> $OUT/bench.err
 for W in 20msps 2msps; do
-  timeout 400 python bench.py --workload $W --no-cpu-baseline > $OUT/bench_${W}.json 2>> $OUT/bench.err
+  timeout 400 python bench.py --full --workload $W --no-cpu-baseline > $OUT/bench_${W}.json 2>> $OUT/bench.err
   for K in 4 8 16; do
-    timeout 400 python bench.py --workload $W --streams $K --no-cpu-baseline --no-extra > $OUT/bench_${W}_k$K.json 2>> $OUT/bench.err
+    timeout 400 python bench.py --full --workload $W --streams $K --no-cpu-baseline --no-extra > $OUT/bench_${W}_k$K.json 2>> $OUT/bench.err
   done
 done
 cat $OUT/tests_gpu.txt; tail -1 $OUT/smoke.txt

@@ -6,10 +6,10 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')
 tail -3 $OUT/smoke.txt
 for W in 20msps 2msps; do
   for F in 1 2 3; do
-    timeout 300 python bench.py --workload $W --streams 8 --inflight $F --steps 24 --warmup 6 --no-cpu-baseline --no-extra > $OUT/bench_${W}_k8_f$F.json 2>> $OUT/bench.err
+    timeout 300 python bench.py --full --workload $W --streams 8 --inflight $F --steps 24 --warmup 6 --no-cpu-baseline --no-extra > $OUT/bench_${W}_k8_f$F.json 2>> $OUT/bench.err
   done
 done
-timeout 300 python bench.py --replicas --streams 8 --no-cpu-baseline --no-extra > $OUT/bench_replicas1_k8.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --replicas --streams 8 --no-cpu-baseline --no-extra > $OUT/bench_replicas1_k8.json 2>> $OUT/bench.err
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/kflight/bench_*.json')):

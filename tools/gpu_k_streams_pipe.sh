@@ -5,10 +5,10 @@ OUT=gpurun_out/kpipe; rm -rf $OUT; mkdir -p $OUT
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $OUT/tests_gpu.txt
 cat $OUT/tests_gpu.txt
 for W in 20msps 2msps; do
-  timeout 400 python bench.py --workload $W --no-cpu-baseline > $OUT/bench_${W}.json 2>> $OUT/bench.err
+  timeout 400 python bench.py --full --workload $W --no-cpu-baseline > $OUT/bench_${W}.json 2>> $OUT/bench.err
 done
-timeout 300 python bench.py --streams 2 --no-cpu-baseline --no-extra > $OUT/bench_64msps_k2.json 2>> $OUT/bench.err
-timeout 300 python bench.py --no-cpu-baseline --no-extra > $OUT/bench_64msps.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --streams 2 --no-cpu-baseline --no-extra > $OUT/bench_64msps_k2.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --no-cpu-baseline --no-extra > $OUT/bench_64msps.json 2>> $OUT/bench.err
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/kpipe/bench_*.json')):

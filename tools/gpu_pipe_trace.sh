@@ -1,8 +1,9 @@
 # do the kernels of batches in flight overlap?  kernel trace of the pipelined loop:   gpurun -- 'bash tools/gpu_pipe_trace.sh'
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pipetrace
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 9 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o bench -- python $ROOT/bench.py --steps 9 --warmup 1 --full --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
 cd $GRAFT_REPO_ROOT
 python - <<'PY'
 import csv, glob

@@ -161,6 +161,11 @@ class Library(object):
         L.am_fetch_candidates.argtypes = [vp, vp, vp, vp, vp, u64, pu64]
         L.am_last_frontend.restype = C.c_int
         L.am_last_frontend.argtypes = [vp]
+        L.am_sample_bytes.restype = C.c_size_t
+        L.am_sample_bytes.argtypes = [ci]
+        L.am_unpack.argtypes = [vp, vp, u64, ci, u32, vp]
+        L.am_synchronize.argtypes = [vp]
+        L.am_process_samples.argtypes = [vp, vp, u64, ci, u32, vp, u64, pu64]
         self.L = L
         if L.am_abi_version() != ABI_VERSION:
             raise OSError("ABI version mismatch in %s" % path)
@@ -373,6 +378,39 @@ class Context(object):
         return self._process(int(dev_ptr), int(n_complex), AM_F_DEVICE_IN | (AM_F_FLUSH if flush else 0) |
                              (AM_F_KEEP_TAGS if keep_tags else 0), capacity)
 
+    # native sample formats (air_modes/formats.py): raw integer I,Q, widened on the device
+    def process_samples(self, raw, fmt=None, flush=False, capacity=None, keep_tags=False):
+        """Host samples in a native format (int16 / int8 / uint8 components, I,Q interleaved flat or shape (n, 2); float32 /
+        complex64 is cf32) -> accepted packets of this chunk.  fmt: the format's name, None = from the dtype."""
+        from . import formats
+        a, name = formats.raw_components(raw, fmt)
+        n = a.size // 2
+        return self._process(a.ctypes.data if n else None, n,
+                             (AM_F_FLUSH if flush else 0) | (AM_F_KEEP_TAGS if keep_tags else 0), capacity, formats.code(name))
+
+    def process_samples_device(self, dev_ptr, n_complex, fmt, flush=False, capacity=None, keep_tags=False):
+        """The same with the raw samples already in this GPU's memory."""
+        from . import formats
+        return self._process(int(dev_ptr), int(n_complex), AM_F_DEVICE_IN | (AM_F_FLUSH if flush else 0) |
+                             (AM_F_KEEP_TAGS if keep_tags else 0), capacity, formats.code(fmt))
+
+    def unpack(self, raw, fmt, out_ptr, n_complex=None):
+        """The conversion alone (am_unpack), enqueued on the context's stream: raw = a host array (its dtype must be fmt's),
+        or a device pointer with n_complex given; out_ptr: device memory for 2 * n float32.  Returns n."""
+        from . import formats
+        if n_complex is None:
+            a, name = formats.raw_components(raw, fmt)
+            n, ptr, flags = a.size // 2, a.ctypes.data, 0
+        else:
+            n, ptr, flags, name = int(n_complex), int(raw), AM_F_DEVICE_IN, fmt
+        self._chk(self.lib.L.am_unpack(self._h, C.c_void_p(ptr if n else None), n, formats.code(name), flags,
+                                       C.c_void_p(int(out_ptr) or None)))
+        return n
+
+    def synchronize(self):
+        """The host waits for everything enqueued on the context's stream."""
+        self._chk(self.lib.L.am_synchronize(self._h))
+
     # K independent streams in one scan
     def multi_layout(self, lengths):
         """(offsets, total) in complex samples: where K whole streams of the given lengths lie in the ONE buffer
@@ -485,11 +523,14 @@ class Context(object):
                                                      iav.ctypes.data, m, C.byref(n)))
         return pos, ref, val, iav
 
-    def _process(self, ptr, n, flags, capacity):
+    def _process(self, ptr, n, flags, capacity, fmt=None):
         cap = int(capacity) if capacity is not None else max(64, n // 2000 + 64)
         out = self._receive_buffer(cap)
         got = C.c_uint64(0)
-        rc = self.lib.L.am_process_iq(self._h, ptr, n, flags, out.ctypes.data, cap, C.byref(got))
+        if fmt is None:
+            rc = self.lib.L.am_process_iq(self._h, ptr, n, flags, out.ctypes.data, cap, C.byref(got))
+        else:
+            rc = self.lib.L.am_process_samples(self._h, ptr, n, fmt, flags, out.ctypes.data, cap, C.byref(got))
         if rc == AM_ECAPACITY:
             return self._fetch(int(got.value))
         self._chk(rc)
@@ -768,6 +809,7 @@ class Uploader(object):
         L.am_uploader_host.restype = C.c_void_p
         L.am_uploader_host.argtypes = [C.c_void_p, C.c_int]
         L.am_uploader_start.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+        L.am_uploader_start_bytes.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
         L.am_uploader_wait.restype = C.c_void_p
         L.am_uploader_wait.argtypes = [C.c_void_p, C.c_int]
         err = C.c_int(0)
@@ -787,6 +829,12 @@ class Uploader(object):
         rc = self.lib.L.am_uploader_start(self._h, int(slot), int(n_complex))
         if rc != AM_OK:
             raise AirModesError(rc, "am_uploader_start failed")
+
+    def start_bytes(self, slot, nbytes):
+        """Start the copy of the slot's first nbytes bytes (raw samples of a native format; the slot holds capacity * 8)."""
+        rc = self.lib.L.am_uploader_start_bytes(self._h, int(slot), int(nbytes))
+        if rc != AM_OK:
+            raise AirModesError(rc, "am_uploader_start_bytes failed")
 
     def wait(self, slot):
         ptr = self.lib.L.am_uploader_wait(self._h, int(slot))

@@ -2,11 +2,17 @@
 python/radio.py:90-118,221-234):
 
     python -m air_modes.modes_rx -s capture.cf32 -r 2e6 [-T 7.0] [--no-pmf] [-l lat,lon] [-n] [--raw]
+    python -m air_modes.modes_rx -s rtlsdr.cu8 -r 2.4e6            (-f cu8 when the name does not say it)
 
 Reads a gr_complex file (interleaved little-endian float32 I,Q -- what
 blocks.file_source(gr.sizeof_gr_complex, path) reads), pushes it through air_modes.rx_path on
 the GPU chunk by chunk, and prints one line per decoded report in the reference's format
 (python/msprint.py), or the slicer's raw messages with --raw.
+
+-f / --format: the file holds a radio's native samples instead -- sc16 (USRP, Airspy, most recorders), cs8 (HackRF),
+cu8 (RTL-SDR); little-endian I,Q pairs, no header.  The reference's sources widen them on the host
+(python/radio.py:164-231); here the raw bytes go through the pinned buffer to the device and are widened there
+(air_modes/formats.py is the definition): 2 or 4 times fewer bytes read, pinned and sent over PCIe.
 
 Input slower than 4 Msps is resampled to 4 Msps first, as modes_radio does (python/radio.py:49-53) -- with this
 package's own polyphase interpolator (air_modes/resample.py: GNU Radio's taps are not reproducible here, so that
@@ -22,12 +28,14 @@ import sys
 
 import numpy as np
 
-from . import resample
+from . import formats, resample
 
 
 def build_parser():
     ap = argparse.ArgumentParser(prog="modes_rx", description=__doc__.split("\n\n")[0])
-    ap.add_argument("-s", "--source", required=True, help="gr_complex (cf32) file")        # radio.py:94
+    ap.add_argument("-s", "--source", required=True, help="sample file: gr_complex (cf32), or see -f")   # radio.py:94
+    ap.add_argument("-f", "--format", choices=["cf32", "sc16", "cs8", "cu8"], default=None,
+                    help="sample format of the file [default: by suffix .cu8 .cs8 .sc16 .cs16, else cf32]")
     ap.add_argument("-r", "--rate", type=float, default=4e6, help="sample rate [default=%(default)s]")   # :112
     ap.add_argument("-T", "--threshold", type=float, default=7.0,
                     help="pulse detection threshold above noise in dB [default=%(default)s]")            # :114
@@ -44,9 +52,20 @@ def build_parser():
     return ap
 
 
+def source_format(path, fmt=None):
+    """The format of a sample file: the one given, else by the name's suffix, else cf32."""
+    if fmt:
+        return fmt
+    for suffix, name in formats.SUFFIXES.items():
+        if path.lower().endswith(suffix):
+            return name
+    return "cf32"
+
+
 def main(argv=None, out=None):
     args = build_parser().parse_args(argv)
     out = out or sys.stdout
+    fmt = source_format(args.source, args.format)
     from . import cpr_decoder, make_parser, msg_queue, output_print, pubsub, rx_path
 
     queue = msg_queue()
@@ -72,7 +91,14 @@ def main(argv=None, out=None):
     from . import _capi
     nslots = 2
     drain = resample.TAPS_PER_PHASE if resampler is not None else 0
-    up = _capi.Uploader(args.chunk + drain, nslots=nslots)
+    bps = formats.bytes_per_sample(fmt)
+    raw = fmt != "cf32"
+    # a slot holds a chunk at its raw width; in front of the interpolator (float32 in, on the device) the widened chunk and
+    # its drain zeros follow the raw bytes in the slot's device twin
+    float_off = (args.chunk * bps + 15) // 16 * 16 if raw and resampler is not None else 0
+    slot_bytes = float_off + 8 * (args.chunk + drain) if float_off or not raw else args.chunk * bps
+    up = _capi.Uploader((slot_bytes + 7) // 8, nslots=nslots)
+    drain_zeros = np.zeros(drain, np.complex64)
     ready = _queue.Queue()                    # (slot, samples, last) in stream order, or an exception
     free = _queue.Queue()
     for k in range(nslots):
@@ -84,15 +110,18 @@ def main(argv=None, out=None):
                 while True:
                     slot = free.get()
                     buf = up.buffer(slot)
-                    want = 8 * args.chunk
+                    want = bps * args.chunk
                     got = f.readinto(memoryview(buf).cast("B")[:want])
-                    n = got // 8                                      # whole complex samples
+                    n = got // bps                                    # whole complex samples
                     last = got < want
-                    if last and drain:
-                        # drain: the interpolator holds its last outputs back until it has seen what follows them
-                        buf[2 * n:2 * (n + drain)] = 0.0
-                        n += drain
-                    up.start(slot, n)
+                    if raw:
+                        up.start_bytes(slot, n * bps)                 # (raw zero bytes are not zero samples: the drain comes later)
+                    else:
+                        if last and drain:
+                            # drain: the interpolator holds its last outputs back until it has seen what follows them
+                            buf[2 * n:2 * (n + drain)] = 0.0
+                            n += drain
+                        up.start(slot, n)
                     ready.put((slot, n, last))
                     if last:
                         return
@@ -106,9 +135,20 @@ def main(argv=None, out=None):
         if isinstance(slot, Exception):
             raise slot
         ptr = up.wait(slot)
-        if resampler is not None:
-            ptr, n = resampler.work_device_in(ptr, n)                 # (python/radio.py:49-53) 2 -> 4 Msps on the GPU
-        rx.work_device(ptr, n, flush=last)
+        if raw and resampler is not None:
+            # widen behind the raw bytes, append the drain zeros as float32, then as for a cf32 file
+            ctx, fptr = rx.context(), ptr + float_off
+            ctx.unpack(ptr, fmt, fptr, n_complex=n)
+            if last:
+                ctx.unpack(drain_zeros, "cf32", fptr + 8 * n)
+                n += drain
+            ctx.synchronize()                                         # (the interpolator runs on a stream of its own)
+            ptr, n = resampler.work_device_in(fptr, n)
+            rx.work_device(ptr, n, flush=last)
+        else:
+            if resampler is not None:
+                ptr, n = resampler.work_device_in(ptr, n)             # (python/radio.py:49-53) 2 -> 4 Msps on the GPU
+            rx.work_device(ptr, n, flush=last, fmt=fmt)               # (raw samples are widened straight behind the carried tail)
         free.put(slot)                                                # (the call returned: the device is done with the slot)
         while not queue.empty_p():
             text = queue.delete_head().to_string()

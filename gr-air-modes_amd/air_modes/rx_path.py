@@ -52,18 +52,27 @@ class rx_path(object):
         self._ctx.set_rx_time(offset, secs, frac)
 
     def work(self, iq, flush=False, rx_time=()):
-        """Consume a chunk of the gr_complex stream (complex64 array or interleaved float32);
+        """Consume a chunk of the stream: complex64 / interleaved float32 (the gr_complex stream), or raw samples in a
+        radio's native format -- int16 (sc16), int8 (cs8) or uint8 (cu8) components, I,Q interleaved flat or shape (n, 2);
+        the format follows from the dtype (air_modes/formats.py) and the widening runs on the GPU.
         flush=True marks the end of the stream.  rx_time: the (offset, secs, frac) "rx_time" tags that
         fall into this chunk, offsets counted over the whole stream.  Returns the accepted packets
         (structured array) after posting their messages to the queue."""
         for tag in rx_time:
             self._ctx.set_rx_time(*tag)
+        a = np.asarray(iq)
+        if a.dtype in (np.int16, np.int8, np.uint8):
+            pk = self._ctx.process_samples(a, flush=flush)
+            return self._account(pk, a.size // 2)
         pk = self._ctx.process_iq(iq, flush=flush)
-        return self._account(pk, (np.asarray(iq).size // (1 if np.iscomplexobj(iq) else 2)))
+        return self._account(pk, (a.size // (1 if np.iscomplexobj(iq) else 2)))
 
-    def work_device(self, dev_ptr, n_complex, flush=False):
-        """Same with the samples already resident in this GPU's memory (interleaved f32)."""
-        pk = self._ctx.process_iq_device(dev_ptr, n_complex, flush=flush)
+    def work_device(self, dev_ptr, n_complex, flush=False, fmt="cf32"):
+        """Same with the samples already resident in this GPU's memory (interleaved f32, or raw samples of format fmt)."""
+        if fmt == "cf32":
+            pk = self._ctx.process_iq_device(dev_ptr, n_complex, flush=flush)
+        else:
+            pk = self._ctx.process_samples_device(dev_ptr, n_complex, fmt, flush=flush)
         return self._account(pk, n_complex)
 
     def _account(self, pk, n):

@@ -136,6 +136,7 @@ struct am_ctx {
     DevBuf carry, carry2;
 
     // work buffers (grow only)
+    DevBuf raw_in;                // raw bytes of a host chunk in a native sample format (am_process_samples, am_unpack)
     DevBuf src, bb, avg, cand_seg, inavg, blk_cnt, blk_off, pos, e, tgt, valid,
         jump, emit_idx, dcount, off_local, blk_tot2, blk_base2, energy, bits, seg_base,
         cblk_cnt, cblk_off, scalars, bursts, tags, packets, crc_pow, recs, cscratch, dc_m1, dc_y, wgmax;
@@ -1032,7 +1033,7 @@ void am_destroy(am_ctx *c)
                 c->ht_n, c->ht[0] / c->ht_n, c->ht[1] / c->ht_n, c->ht[2] / c->ht_n, c->ht[5] / c->ht_n, c->ht[3] / c->ht_n, c->ht[4] / c->ht_n, c->ht[6], c->ht[7] / c->ht_n);
 #endif
     (void)hipSetDevice(c->device);
-    DevBuf *all[] = {&c->pb_bb, &c->pb_avg, &c->bbmax, &c->carry, &c->carry2, &c->src, &c->bb, &c->avg, &c->cand_seg, &c->inavg, &c->dcount, &c->off_local, &c->blk_tot2, &c->blk_base2,
+    DevBuf *all[] = {&c->raw_in, &c->pb_bb, &c->pb_avg, &c->bbmax, &c->carry, &c->carry2, &c->src, &c->bb, &c->avg, &c->cand_seg, &c->inavg, &c->dcount, &c->off_local, &c->blk_tot2, &c->blk_base2,
                      &c->energy, &c->bits, &c->seg_base, &c->blk_cnt, &c->blk_off,
                      &c->pos, &c->e, &c->tgt, &c->valid, &c->jump, &c->emit_idx,
                      &c->lb_dc, &c->lb_mark, &c->cblk_cnt, &c->cblk_off, &c->scalars, &c->bursts, &c->tags, &c->packets, &c->crc_pow,
@@ -1141,14 +1142,42 @@ int am_reset(am_ctx *c)
     return AM_OK;
 }
 
-// am_process_iq, or with `submit` its first half: everything is enqueued, the wait for the scan and what follows it
-// (packets, stream state) is left to am_collect.  submit needs AM_F_FLUSH: batches in flight are independent streams.
-static int process_iq_core(am_ctx *c, const float *iq, uint64_t n, uint32_t flags, am_packet *out, uint64_t cap,
+// n complex samples of format fmt at raw (host, or device with dev_in) -> 2 n floats at out (device), enqueued on the
+// context's stream.  Host input goes to the context's staging buffer at its raw width first.
+static int unpack_into(am_ctx *c, const void *raw, uint64_t n, int fmt, bool dev_in, float *out)
+{
+    if (!n) return AM_OK;
+    const size_t bytes = (size_t)n * am_sample_bytes(fmt);
+    if (fmt == AM_FMT_CF32) {
+        HIPCHK(c, hipMemcpyAsync(out, raw, bytes, dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        return AM_OK;
+    }
+    if (!dev_in) {
+        ENSURE(c, c->raw_in, bytes);
+        HIPCHK(c, hipMemcpyAsync(c->raw_in.p, raw, bytes, hipMemcpyHostToDevice, c->stream));
+        raw = c->raw_in.p;
+    }
+    hipError_t rc = am_launch_unpack(fmt, raw, n, out, c->stream);
+    if (rc != hipSuccess) return fail(c, AM_EHIP, "am_k_unpack launch", rc);
+    return AM_OK;
+}
+
+static int check_samples(am_ctx *c, const void *raw, uint64_t n, int fmt)
+{
+    if (am_sample_bytes(fmt) == 0) return fail(c, AM_EINVAL, "unknown sample format (AM_FMT_CF32 / SC16 / CS8 / CU8)");
+    if (n && !raw) return fail(c, AM_EINVAL, fmt == AM_FMT_CF32 ? "null iq" : "null samples");
+    return AM_OK;
+}
+
+// am_process_iq / am_process_samples, or with `submit` the first half: everything is enqueued, the wait for the scan and
+// what follows it (packets, stream state) is left to am_collect.  submit needs AM_F_FLUSH: batches in flight are independent
+// streams.  fmt: the format of `in` (AM_FMT_CF32: interleaved float32); it matters in step 1 only.
+static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint32_t flags, am_packet *out, uint64_t cap,
                            uint64_t *n_out, bool submit)
 {
     if (!c) return AM_EINVAL;
     if (n_out) *n_out = 0;
-    if (n && !iq) return fail(c, AM_EINVAL, "null iq");
+    if (int rc = check_samples(c, in, n, fmt); rc != AM_OK) return rc;
     if (c->pend.active) return fail(c, AM_EINVAL, "a submitted batch has not been collected (am_collect)");
     if (submit && !(flags & AM_F_FLUSH)) return fail(c, AM_EINVAL, "am_submit_iq needs AM_F_FLUSH (independent batches)");
     const double T0 = am_now_us();
@@ -1172,8 +1201,8 @@ static int process_iq_core(am_ctx *c, const float *iq, uint64_t n, uint32_t flag
     // 1. one contiguous device view of [src_abs0, S1): carried tail + new samples
     const float *src = nullptr;
     uint64_t src_abs0 = c->total_in;
-    if (c->carry_n == 0 && dev_in) {
-        src = iq;                                       // zero copy
+    if (c->carry_n == 0 && dev_in && fmt == AM_FMT_CF32) {
+        src = static_cast<const float *>(in);           // zero copy
     } else if (c->carry_n + n > 0) {
         ENSURE(c, c->src, (c->carry_n + n) * 2 * sizeof(float));
         float *d = (float *)c->src.p;
@@ -1182,9 +1211,8 @@ static int process_iq_core(am_ctx *c, const float *iq, uint64_t n, uint32_t flag
                                      c->stream));
             src_abs0 = c->carry_abs0;
         }
-        if (n)
-            HIPCHK(c, hipMemcpyAsync(d + c->carry_n * 2, iq, n * 2 * sizeof(float),
-                                     dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        // the new samples behind the carried ones: a copy (float32), or the raw bytes widened into their place (am_k_unpack)
+        if (int rc = unpack_into(c, in, n, fmt, dev_in, d + c->carry_n * 2); rc != AM_OK) return rc;
         src = d;
     }
     const uint64_t S1 = c->total_in + n;
@@ -1311,7 +1339,35 @@ static int process_iq_core(am_ctx *c, const float *iq, uint64_t n, uint32_t flag
 int am_process_iq(am_ctx *c, const float *iq, uint64_t n, uint32_t flags, am_packet *out, uint64_t cap,
                   uint64_t *n_out)
 {
-    return process_iq_core(c, iq, n, flags, out, cap, n_out, false);
+    return process_iq_core(c, iq, n, AM_FMT_CF32, flags, out, cap, n_out, false);
+}
+
+int am_process_samples(am_ctx *c, const void *raw, uint64_t n, int fmt, uint32_t flags, am_packet *out, uint64_t cap,
+                       uint64_t *n_out)
+{
+    return process_iq_core(c, raw, n, fmt, flags, out, cap, n_out, false);
+}
+
+int am_unpack(am_ctx *c, const void *raw, uint64_t n, int fmt, uint32_t flags, float *out_dev)
+{
+    if (!c) return AM_EINVAL;
+    if (int rc = check_samples(c, raw, n, fmt); rc != AM_OK) return rc;
+    if (n && !out_dev) return fail(c, AM_EINVAL, "null output");
+    if (n > ((uint64_t)1 << 31)) return fail(c, AM_EINVAL, "chunk larger than 2^31 samples");
+    if (!n) return AM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool dev_in = (flags & AM_F_DEVICE_IN) != 0;
+    if (int rc = unpack_into(c, raw, n, fmt, dev_in, out_dev); rc != AM_OK) return rc;
+    if (!dev_in) HIPCHK(c, hipStreamSynchronize(c->stream));     // the caller's buffer is free again
+    return AM_OK;
+}
+
+int am_synchronize(am_ctx *c)
+{
+    if (!c) return AM_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AM_OK;
 }
 
 // ---- K independent streams in ONE scan (the 2 / 20 Msps configurations off the launch floor) -----------------
@@ -1392,7 +1448,7 @@ int am_process_multi(am_ctx *c, float *iq, uint32_t k, const uint64_t *n, uint32
     uint64_t total = 0;
     int rc = multi_begin(c, iq, k, n, flags, &total);
     if (rc != AM_OK) return rc;
-    rc = process_iq_core(c, iq, total, (flags & AM_F_DEVICE_IN) | AM_F_FLUSH, out, cap, n_out, false);
+    rc = process_iq_core(c, iq, total, AM_FMT_CF32, (flags & AM_F_DEVICE_IN) | AM_F_FLUSH, out, cap, n_out, false);
     if (count) for (uint32_t j = 0; j < k; j++) count[j] = j < c->multi_cnt.size() ? c->multi_cnt[j] : 0;
     if (rc != AM_OK && rc != AM_ECAPACITY) { c->multi_off.clear(); c->multi_em.clear(); }
     return rc;
@@ -1408,7 +1464,7 @@ int am_submit_multi(am_ctx *c, float *iq, uint32_t k, const uint64_t *n, uint32_
     uint64_t total = 0;
     int rc = multi_begin(c, iq, k, n, flags, &total);
     if (rc != AM_OK) return rc;
-    rc = process_iq_core(c, iq, total, (flags & AM_F_DEVICE_IN) | AM_F_FLUSH, nullptr, 0, nullptr, true);
+    rc = process_iq_core(c, iq, total, AM_FMT_CF32, (flags & AM_F_DEVICE_IN) | AM_F_FLUSH, nullptr, 0, nullptr, true);
     if (rc != AM_OK) { c->multi_off.clear(); c->multi_em.clear(); }
     return rc;
 }
@@ -1424,7 +1480,7 @@ int am_multi_counts(am_ctx *c, uint64_t *count, uint32_t k)
 
 int am_submit_iq(am_ctx *c, const float *iq, uint64_t n, uint32_t flags)
 {
-    return process_iq_core(c, iq, n, flags, nullptr, 0, nullptr, true);
+    return process_iq_core(c, iq, n, AM_FMT_CF32, flags, nullptr, 0, nullptr, true);
 }
 
 int am_collect(am_ctx *c, am_packet *out, uint64_t cap, uint64_t *n_out)

@@ -157,6 +157,10 @@ unsigned long long am_dcblock_history(int spc);
 hipError_t am_launch_dcblock(const float *raw, long long raw_abs0, long long raw_abs1, long long y_abs0, long long y_n,
                              int spc, float *m1, float *y, hipStream_t s);
 
+/* ---- native sample formats (am_resample.hip): n complex samples of AM_FMT_SC16 / CS8 / CU8 at raw (device, aligned to its
+ * component) -> 2 n floats at out (device, 8-byte aligned) */
+hipError_t am_launch_unpack(int fmt, const void *raw, uint64_t n, float *out, hipStream_t s);
+
 /* Launchers that take a candidate count M also take an optional device pointer Mp: when given, the
  * kernels use min(M, *Mp), so that the host may launch for a capacity without knowing the count. */
 /* ---- preamble detection / refinement / greedy chain ----------------------------------- */

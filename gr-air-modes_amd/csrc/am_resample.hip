@@ -14,6 +14,9 @@
 // every product and every sum one IEEE double rounding (contraction off).  The taps come from the caller (numpy's
 // kaiser / sinc are not reproduced here).  The host part -- how many outputs a block yields, the carried position and
 // the last 8 input samples -- repeats resample.py's scalar double arithmetic, including its blocks of 2^17 inputs.
+//
+// Also in this file, the other input-side stages: am_k_unpack (native sample formats sc16 / cs8 / cu8 -> float32, the
+// definition is air_modes/formats.py) and the pinned uploader of a host source.
 #include "am_internal.h"
 
 #include <math.h>
@@ -211,6 +214,199 @@ int am_resampler_work(am_resampler *h, const float *iq, uint64_t n, uint32_t fla
 
 } // extern "C"
 
+/* ---- native sample formats: raw integer I,Q -> float32 I,Q (python/radio.py:164-231) -----------------------------
+ * The reference's sources convert on the host before rx_path sees a sample (uhd cpu_format="fc32", osmosdr.source); here the
+ * raw bytes cross PCIe and the widening runs on the device, in front of the front end.  DEFINITION: air_modes/formats.py
+ *
+ *   sc16  float(x) * 2^-15        cs8  float(x) * 2^-7        cu8  (float(x) - 127.5f) * 2^-7
+ *
+ * Every operation is exact in float32 (|x| < 2^16; x - 127.5 has 9 significant bits; a power-of-two scale), so forms that
+ * are equal over the reals are equal bit for bit, and the kernel picks the cheapest:
+ *   cu8   v_cvt_f32_ubyteN, then ONE fma: u * 2^-7 - 127.5 * 2^-7 (the exact value is representable, so the single rounding
+ *         of the fma returns it)
+ *   cs8   x + 128 = the byte with its top bit flipped, read as unsigned: one v_xor per FOUR components, then the cu8 pair
+ *         with -1.0 as the addend
+ *   sc16  sign-extending extract, v_cvt_f32_i32, one multiply
+ * A stream of COMPONENTS, not of samples: the raw pointer is aligned to its component only, so the 16-byte body may begin
+ * in the middle of a sample.  Body: 16-byte loads aligned on the RAW side (nt: every raw byte is read once), 16-byte stores at
+ * the 4-byte alignment that leaves (plain policy: the front end reads the floats next, and a chunk fits the Infinity Cache).
+ * Head and tail (fewer than 16 components each) go one component per thread.  Nothing outside [raw, raw + nc * CS) is read,
+ * nothing outside [out, out + nc) written. */
+template <int FMT> struct unp_fmt;
+template <> struct unp_fmt<AM_FMT_SC16> { static constexpr int CS = 2; };
+template <> struct unp_fmt<AM_FMT_CS8> { static constexpr int CS = 1; };
+template <> struct unp_fmt<AM_FMT_CU8> { static constexpr int CS = 1; };
+
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef unsigned int unp_u4 __attribute__((ext_vector_type(4)));
+typedef float unp_f4a __attribute__((ext_vector_type(4), aligned(4)));
+#endif
+
+__device__ __forceinline__ uint4 unp_load16(const unsigned char *p)          // p: 16-byte aligned
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unp_u4 t = __builtin_nontemporal_load(reinterpret_cast<const unp_u4 *>(p));
+    uint4 r; r.x = t.x; r.y = t.y; r.z = t.z; r.w = t.w;
+    return r;
+#else
+    uint4 r;
+    memcpy(&r, p, 16);
+    return r;
+#endif
+}
+
+__device__ __forceinline__ void unp_store16(float *p, const float *f)        // p: 4-byte aligned
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    unp_f4a t; t.x = f[0]; t.y = f[1]; t.z = f[2]; t.w = f[3];
+    *reinterpret_cast<unp_f4a *>(p) = t;
+#else
+    memcpy(p, f, 16);
+#endif
+}
+
+// one component, the definition as written (head and tail)
+template <int FMT>
+__device__ __forceinline__ float unp_one(const unsigned char *p)
+{
+    if (FMT == AM_FMT_SC16) return (float)(int)*reinterpret_cast<const int16_t *>(p) * 0x1p-15f;
+    if (FMT == AM_FMT_CS8) return (float)(int)*reinterpret_cast<const signed char *>(p) * 0x1p-7f;
+    return ((float)(int)*p - 127.5f) * 0x1p-7f;
+}
+
+// the 16 / CS components of one 32-bit word
+template <int FMT>
+__device__ __forceinline__ void unp_word(uint32_t w, float *f)
+{
+    if (FMT == AM_FMT_SC16) {
+        f[0] = (float)(int)(int16_t)(w & 0xffffu) * 0x1p-15f;
+        f[1] = (float)((int32_t)w >> 16) * 0x1p-15f;
+    } else {
+        const float c = FMT == AM_FMT_CS8 ? -1.0f : -127.5f * 0x1p-7f;
+        if (FMT == AM_FMT_CS8) w ^= 0x80808080u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) f[k] = fmaf((float)((w >> (8 * k)) & 0xffu), 0x1p-7f, c);
+    }
+}
+
+// value of `v` in lane j of the caller's group of four lanes (DPP quad_perm:[j,j,j,j])
+template <int J>
+__device__ __forceinline__ uint32_t unp_quad_bcast(uint32_t v, int lane)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)lane;
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, J * 0x55, 0xf, 0xf, true);
+#else
+    return __shfl(v, (lane & ~3) + J, AM_WAVE);
+#endif
+}
+
+// word q (= lane & 3) of the 16 bytes that lane J of the quad loaded
+template <int J>
+__device__ __forceinline__ uint32_t unp_quad_word(const uint4 &w, int lane)
+{
+    const uint32_t t0 = unp_quad_bcast<J>(w.x, lane), t1 = unp_quad_bcast<J>(w.y, lane);
+    const uint32_t t2 = unp_quad_bcast<J>(w.z, lane), t3 = unp_quad_bcast<J>(w.w, lane);
+    const uint32_t lo = (lane & 1) ? t1 : t0, hi = (lane & 1) ? t3 : t2;        // (two levels of v_cndmask, no branch)
+    return (lane & 2) ? hi : lo;
+}
+
+// one wave-uniform step of the 8-bit body: lane `lane` loads vector v (if it exists), the quad exchanges words, and store
+// j of a lane writes piece q of the vector that the quad's lane j loaded.  FULL: all 64 vectors of the step exist.
+template <int FMT, bool FULL>
+__device__ __forceinline__ void unp_step8(const unsigned char *vb, float *ob, unsigned long long v, unsigned long long nvec, int lane)
+{
+    uint4 w; w.x = w.y = w.z = w.w = 0u;
+    if (FULL || v < nvec) w = unp_load16(vb + v * 16);
+    const uint32_t o0 = unp_quad_word<0>(w, lane), o1 = unp_quad_word<1>(w, lane);
+    const uint32_t o2 = unp_quad_word<2>(w, lane), o3 = unp_quad_word<3>(w, lane);
+    const int q = lane & 3;
+    const unsigned long long vq = v - (unsigned)q;                               // the vector the quad's lane 0 loaded
+    float *p = ob + vq * 16 + 4 * q;
+    float f[4];
+    if (FULL || vq + 0 < nvec) { unp_word<FMT>(o0, f); unp_store16(p, f); }
+    if (FULL || vq + 1 < nvec) { unp_word<FMT>(o1, f); unp_store16(p + 16, f); }
+    if (FULL || vq + 2 < nvec) { unp_word<FMT>(o2, f); unp_store16(p + 32, f); }
+    if (FULL || vq + 3 < nvec) { unp_word<FMT>(o3, f); unp_store16(p + 48, f); }
+}
+
+#define AM_UNPACK_THREADS 256
+template <int FMT>
+__global__ void __launch_bounds__(AM_UNPACK_THREADS)
+am_k_unpack(const unsigned char *__restrict__ raw, unsigned long long nc, float *__restrict__ out)
+{
+    constexpr int CS = unp_fmt<FMT>::CS, CPW = 4 / CS, CPV = 16 / CS;            // bytes per component; components per word / per load
+    unsigned long long head = ((16u - (unsigned)(reinterpret_cast<unsigned long long>(raw) & 15u)) & 15u) / CS;
+    if (head > nc) head = nc;
+    const unsigned long long nvec = (nc - head) / CPV;
+    const unsigned long long tail0 = head + nvec * CPV;
+    const unsigned long long g = (unsigned long long)blockIdx.x * AM_UNPACK_THREADS + threadIdx.x;
+    const unsigned long long stride = (unsigned long long)gridDim.x * AM_UNPACK_THREADS;
+    const unsigned char *vb = raw + head * CS;
+    float *ob = out + head;
+    if (CS == 2) {
+        // a lane stores the 32 bytes of floats of its own load
+        for (unsigned long long v = g; v < nvec; v += stride) {
+            const uint4 w = unp_load16(vb + v * 16);
+            float f[CPV];
+            unp_word<FMT>(w.x, f);
+            unp_word<FMT>(w.y, f + CPW);
+            unp_word<FMT>(w.z, f + 2 * CPW);
+            unp_word<FMT>(w.w, f + 3 * CPW);
+#pragma unroll
+            for (int j = 0; j < CPV / 4; ++j) unp_store16(ob + v * CPV + 4 * j, f + 4 * j);
+        }
+    } else {
+        // One load widens to 64 bytes: stored by the lane that loaded them, a store instruction would touch a quarter of 64
+        // different 64-byte lines (measured: 7 % slower than a device-to-device copy of the same output, which moves MORE
+        // bytes).  So the four lanes of a quad exchange words first: store j of a quad writes, as four adjacent 16-byte pieces,
+        // the whole line that the quad's lane j loaded -- 16 whole lines per instruction.  The loop is uniform over the wave
+        // (every lane takes part in the exchange); loads and stores past the last vector are masked.
+        const int lane = (int)(threadIdx.x & (AM_WAVE - 1));
+        for (unsigned long long v0 = g - (unsigned)lane; v0 < nvec; v0 += stride) {
+            if (v0 + AM_WAVE <= nvec) unp_step8<FMT, true>(vb, ob, v0 + (unsigned)lane, nvec, lane);
+            else unp_step8<FMT, false>(vb, ob, v0 + (unsigned)lane, nvec, lane);
+        }
+    }
+    if (g < head) out[g] = unp_one<FMT>(raw + g * CS);
+    if (g < nc - tail0) out[tail0 + g] = unp_one<FMT>(raw + (tail0 + g) * CS);
+}
+
+template <int FMT>
+static hipError_t unp_launch(const void *raw, uint64_t n, float *out, hipStream_t s)
+{
+    const unsigned long long nc = 2ull * n;
+    const unsigned long long nvec = nc / (16 / unp_fmt<FMT>::CS) + 1;               // (an upper bound: the head may take one away)
+    // a grid the chip holds at once (8 workgroups of 4 waves per CU: a 16-byte load per lane = 32 KiB in flight per CU), strided
+    unsigned long long blocks = (nvec + AM_UNPACK_THREADS - 1) / AM_UNPACK_THREADS;
+    const unsigned long long resident = 8ull * (unsigned long long)am_device_cus();
+    if (blocks > resident) blocks = resident;
+    hipLaunchKernelGGL(am_k_unpack<FMT>, dim3((unsigned)blocks), dim3(AM_UNPACK_THREADS), 0, s,
+                       static_cast<const unsigned char *>(raw), nc, out);
+    return hipGetLastError();
+}
+
+hipError_t am_launch_unpack(int fmt, const void *raw, uint64_t n, float *out, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    switch (fmt) {
+    case AM_FMT_SC16: return unp_launch<AM_FMT_SC16>(raw, n, out, s);
+    case AM_FMT_CS8: return unp_launch<AM_FMT_CS8>(raw, n, out, s);
+    case AM_FMT_CU8: return unp_launch<AM_FMT_CU8>(raw, n, out, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+extern "C" size_t am_sample_bytes(int fmt)
+{
+    switch (fmt) {
+    case AM_FMT_CF32: return 8;
+    case AM_FMT_SC16: return 4;
+    case AM_FMT_CS8: case AM_FMT_CU8: return 2;
+    default: return 0;
+    }
+}
+
 /* ---- pinned staging: host samples on their way to the device, several buffers in flight --------------------------
  * A file (or socket) reader fills slot k's pinned buffer and starts its copy while the receive path still works on
  * slot k-1's samples on the device: the PCIe transfer of one chunk overlaps the scan of the one before it. */
@@ -268,14 +464,19 @@ void am_uploader_destroy(am_uploader *u)
 
 float *am_uploader_host(am_uploader *u, int slot) { return (u && slot >= 0 && slot < u->nslots) ? u->host[slot] : nullptr; }
 
-int am_uploader_start(am_uploader *u, int slot, uint64_t n_complex)
+int am_uploader_start_bytes(am_uploader *u, int slot, uint64_t nbytes)
 {
-    if (!u || slot < 0 || slot >= u->nslots || n_complex > u->cap) return AM_EINVAL;
+    if (!u || slot < 0 || slot >= u->nslots || nbytes > u->cap * 2 * sizeof(float)) return AM_EINVAL;
     if (hipSetDevice(u->device) != hipSuccess) return AM_EHIP;
-    if (n_complex && hipMemcpyAsync(u->dev[slot], u->host[slot], (size_t)n_complex * 2 * sizeof(float), hipMemcpyHostToDevice,
-                                    u->stream) != hipSuccess)
+    if (nbytes && hipMemcpyAsync(u->dev[slot], u->host[slot], (size_t)nbytes, hipMemcpyHostToDevice, u->stream) != hipSuccess)
         return AM_EHIP;
     return hipEventRecord(u->done[slot], u->stream) == hipSuccess ? AM_OK : AM_EHIP;
+}
+
+int am_uploader_start(am_uploader *u, int slot, uint64_t n_complex)
+{
+    if (!u || n_complex > u->cap) return AM_EINVAL;
+    return am_uploader_start_bytes(u, slot, n_complex * 2 * sizeof(float));
 }
 
 const float *am_uploader_wait(am_uploader *u, int slot)

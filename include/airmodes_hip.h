@@ -430,6 +430,44 @@ AM_API float *am_uploader_host(am_uploader *u, int slot);
 AM_API int am_uploader_start(am_uploader *u, int slot, uint64_t n_complex);
 AM_API const float *am_uploader_wait(am_uploader *u, int slot);
 
+/* the same for raw bytes (native sample formats below; the host side of what replaces python/radio.py:164-231's converting
+ * sources): the pinned slots hold capacity_complex * 8 bytes; start a copy of nbytes raw bytes, am_uploader_wait as before */
+AM_API int am_uploader_start_bytes(am_uploader *u, int slot, uint64_t nbytes);
+
+/* ---- native sample formats (python/radio.py:164-231) ----------------------------------------------------------
+ * The reference's sources hand rx_path float32 whatever the radio delivers: uhd.stream_args(cpu_format="fc32") and
+ * osmosdr.source convert on the host (python/radio.py:164-231).  This package has no such blocks; instead the raw
+ * little-endian integer pairs (I then Q) cross PCIe as they are and are widened on the device, in the context's stream, in
+ * front of the front end.  DEFINITION (air_modes/formats.py; every operation exact in float32, so bit for bit):
+ *   AM_FMT_CF32  float32  x
+ *   AM_FMT_SC16  int16    float(x) * 2^-15
+ *   AM_FMT_CS8   int8     float(x) * 2^-7
+ *   AM_FMT_CU8   uint8    (float(x) - 127.5f) * 2^-7
+ * The packets of a raw stream are the packets of the float32 stream this conversion produces. */
+#define AM_FMT_CF32 0   /* replaces python/radio.py:164-231's host-side conversion: nothing to convert */
+#define AM_FMT_SC16 1   /* python/radio.py:164-231: what a USRP sends over the wire (otw sc16) before uhd widens it */
+#define AM_FMT_CS8  2   /* python/radio.py:164-231: HackRF through osmosdr.source */
+#define AM_FMT_CU8  3   /* python/radio.py:164-231: RTL-SDR through osmosdr.source */
+/* bytes per complex sample; 0 for an unknown format (in place of the item sizes of python/radio.py:164-231's blocks) */
+AM_API size_t am_sample_bytes(int fmt);
+/* The conversion alone (what python/radio.py:164-231's source blocks do before rx_path): raw (host, or device with
+ * AM_F_DEVICE_IN; aligned to its component) -> out_dev (device, 2 * n_complex floats, 8-byte aligned), enqueued on the
+ * context's stream.  With host input the call returns once the raw bytes have left the caller's buffer; with device input
+ * it returns at once, and what follows on the context's stream (am_process_iq with AM_F_DEVICE_IN, ...) is ordered behind
+ * it; a consumer on another stream orders itself with am_signal_stream, or the host waits with am_synchronize.
+ * This is also how callers of the pipes (am_pipe_*, am_spipe_*), of am_process_multi and of the shard calls feed raw data:
+ * they own float32 device buffers already, and those calls take no format argument. */
+AM_API int am_unpack(am_ctx *ctx, const void *raw, uint64_t n_complex, int fmt, uint32_t flags, float *out_dev);
+/* the host waits for everything enqueued on the context's stream so far (am_unpack's output for am_resampler_work, which
+ * runs on a stream of its own: python/radio.py:164-231's source in front of :49-53's resampler) */
+AM_API int am_synchronize(am_ctx *ctx);
+/* am_process_iq on am_unpack's output (rx_path behind python/radio.py:164-231's sources): same flags, same chunking
+ * rules, same results.  Host input: the RAW bytes are copied to a staging buffer of the context and unpacked straight
+ * behind the carried tail, so a sample crosses PCIe once, at its raw width.  AM_FMT_CF32 is am_process_iq itself.
+ * AM_EINVAL for an unknown format or a null pointer with n_complex > 0. */
+AM_API int am_process_samples(am_ctx *ctx, const void *raw, uint64_t n_complex, int fmt, uint32_t flags,
+                              am_packet *out, uint64_t cap, uint64_t *n_out);
+
 /* last error text of the context (or of am_create when ctx == NULL) */
 AM_API const char *am_last_error(const am_ctx *ctx);
 

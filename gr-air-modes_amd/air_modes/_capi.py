@@ -166,6 +166,10 @@ class Library(object):
         L.am_unpack.argtypes = [vp, vp, u64, ci, u32, vp]
         L.am_synchronize.argtypes = [vp]
         L.am_process_samples.argtypes = [vp, vp, u64, ci, u32, vp, u64, pu64]
+        for name in ("am_set_fix_errors", "am_pipe_set_fix_errors", "am_spipe_set_fix_errors"):
+            getattr(L, name).argtypes = [vp, ci]
+        for name in ("am_get_fix_errors", "am_pipe_get_fix_errors", "am_spipe_get_fix_errors"):
+            getattr(L, name).argtypes = [vp]
         self.L = L
         if L.am_abi_version() != ABI_VERSION:
             raise OSError("ABI version mismatch in %s" % path)
@@ -271,6 +275,14 @@ class Context(object):
 
     def get_pmf(self):
         return bool(self.lib.L.am_get_pmf(self._h))
+
+    def set_fix_errors(self, max_bits):
+        """Opt-in repair of DF11 / DF17 replies with up to max_bits (0, 1, 2) wrong bits (am_set_fix_errors; 0 = the
+        reference's drop, lib/slicer_impl.cc:179-182).  A repaired packet has crc 0 and reserved[1] = bits flipped."""
+        self._chk(self.lib.L.am_set_fix_errors(self._h, int(max_bits)))
+
+    def get_fix_errors(self):
+        return int(self.lib.L.am_get_fix_errors(self._h))
 
     def reset(self):
         self._chk(self.lib.L.am_reset(self._h))
@@ -674,6 +686,13 @@ class Pipe(object):
         if rc != AM_OK:
             raise AirModesError(rc, self.lib.L.am_pipe_last_error(self._h).decode())
 
+    def set_fix_errors(self, max_bits):
+        """As Context.set_fix_errors, for every context of the pipe; with no batch in flight."""
+        self._chk(self.lib.L.am_pipe_set_fix_errors(self._h, int(max_bits)))
+
+    def get_fix_errors(self):
+        return int(self.lib.L.am_pipe_get_fix_errors(self._h))
+
     def submit(self, iq):
         """A batch in host memory.  The samples must stay valid until the batch is collected: the (possibly converted)
         array is kept referenced here until then."""
@@ -765,6 +784,13 @@ class StreamPipe(object):
 
     def set_rx_time(self, offset, secs, frac):
         self._chk(self.lib.L.am_spipe_set_rx_time(self._h, int(offset), int(secs), float(frac)))
+
+    def set_fix_errors(self, max_bits):
+        """As Context.set_fix_errors, for the whole stream; with no chunk in flight."""
+        self._chk(self.lib.L.am_spipe_set_fix_errors(self._h, int(max_bits)))
+
+    def get_fix_errors(self):
+        return int(self.lib.L.am_spipe_get_fix_errors(self._h))
 
     def submit_device(self, ptr, n, flush=False):
         self._chk(self.lib.L.am_spipe_submit(self._h, int(ptr), int(n), AM_F_DEVICE_IN | (AM_F_FLUSH if flush else 0)))

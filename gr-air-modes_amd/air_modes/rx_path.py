@@ -13,7 +13,7 @@ from .blocks import slicer as _slicer
 
 
 class rx_path(object):
-    def __init__(self, rate, threshold, queue, use_pmf=False, use_dcblock=False, device=-1, lib=None):
+    def __init__(self, rate, threshold, queue, use_pmf=False, use_dcblock=False, device=-1, lib=None, fix_errors=0):
         self._rate = int(rate)
         self._threshold = threshold
         self._queue = queue
@@ -23,7 +23,10 @@ class rx_path(object):
                                   use_dcblock=use_dcblock, device=device, lib=lib)
         self._slicer = _slicer(queue, _ctx=self._ctx)
         self.packets = 0
+        self.repaired = 0             # ... of them repaired (set_fix_errors)
         self.samples = 0
+        if fix_errors:
+            self.set_fix_errors(fix_errors)
 
     # --- reference surface: python/rx_path.py:67-87 ---
     def set_rate(self, rate):
@@ -44,6 +47,14 @@ class rx_path(object):
 
     def get_threshold(self):
         return self._ctx.get_threshold()
+
+    # --- beyond the reference: it drops every DF11 / DF17 reply that fails parity (lib/slicer_impl.cc:179-182) ---
+    def set_fix_errors(self, max_bits):
+        """Repair replies with up to max_bits (0 = off, 1, 2) wrong bits from the next work() on (am_set_fix_errors)."""
+        self._ctx.set_fix_errors(max_bits)
+
+    def get_fix_errors(self):
+        return self._ctx.get_fix_errors()
 
     # --- what the scheduler does for the reference: push samples through ---
     def set_rx_time(self, offset, secs, frac):
@@ -78,6 +89,7 @@ class rx_path(object):
     def _account(self, pk, n):
         self._slicer.post(pk)
         self.packets += len(pk)
+        self.repaired += int(np.count_nonzero(pk["reserved"][:, 1])) if len(pk) else 0
         self.samples += int(n)
         return pk
 
@@ -92,8 +104,10 @@ class rx_path_bank(object):
     every receiver carries the six significant digits of a fresh ostringstream, lib/slicer_impl.cc:186-192).  Every call is a set
     of WHOLE streams (item counts and time stamps start at 0): the batch form of rx_path.work(capture, flush=True)."""
 
-    def __init__(self, rate, threshold, queues, use_pmf=False, device=-1, lib=None):
+    def __init__(self, rate, threshold, queues, use_pmf=False, device=-1, lib=None, fix_errors=0):
         self._ctx = _capi.Context(float(int(rate)), float(threshold), use_pmf=use_pmf, device=device, lib=lib)
+        if fix_errors:
+            self._ctx.set_fix_errors(fix_errors)
         self._slicers = [_slicer(q, _ctx=self._ctx) for q in queues]
         self.packets = [0] * len(queues)
 

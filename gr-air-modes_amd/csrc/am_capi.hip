@@ -53,6 +53,7 @@ struct am_ctx {
     float thr_db = 0.0f;
     float thr_lin = 0.0f;
     int use_pmf = 0;
+    int fix_bits = 0;             // am_set_fix_errors: wrong bits a DF11 / DF17 reply may be repaired of (0: none, the reference's :179-182)
     int tile = 0;
     // Speculative launches: the candidate count of a scan is only known on the device when its kernels
     // are enqueued.  Instead of a host round trip in the middle of the pipeline, the streaming path
@@ -813,7 +814,8 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
                                              (uint32_t *)c->e.p, base_abs, c->rate_i, (const am_time_tag *)c->tt_dev.p,
                                              (uint32_t)c->tt.size(), keep_dev ? (float *)c->bursts.p : nullptr,
                                              keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p,
-                                             c->pin_packets, (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp));
+                                             c->pin_packets, (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp,
+                                             c->fix_bits));
     else
     HIPCHK(c, am_launch_extract_slice(bb, (const float *)c->inavg.p, c->spc, c->frac ? (const int *)c->chip_idx.p : nullptr,
                                       c->geom.hist0, (const uint4 *)c->emit_idx.p, n_ptr, n_max,
@@ -821,7 +823,7 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
                                       (const am_time_tag *)c->tt_dev.p, (uint32_t)c->tt.size(),
                                       keep_dev ? (float *)c->bursts.p : nullptr,
                                       keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p, c->pin_packets,
-                                      (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp));
+                                      (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp, c->fix_bits));
     if (c->keep_bytes && c->resolving_shard)
         // time shards: the samples the next step needs in front of its chunk, kept while this step's are still in place
         // (am_shard_keep_tail; behind the extraction kernel, which still reads them; complete when the ticket is seen)
@@ -1131,6 +1133,17 @@ int am_signal_stream(am_ctx *c, void *hip_stream)
 double am_get_rate(const am_ctx *c) { return c ? c->rate : 0.0; }
 float am_get_threshold(const am_ctx *c) { return c ? c->thr_db : 0.0f; }
 int am_get_pmf(const am_ctx *c) { return c ? c->use_pmf : 0; }
+
+// slicer_impl.cc:179-182 drops every DF11 / DF17 reply with a bad syndrome; types.h:29-40 carries lowconfbits[] for a repair
+// that was never written.  The setting only selects which slicing kernels the next scan launches (am_slice_wave<FIX>).
+int am_set_fix_errors(am_ctx *c, int max_bits)
+{
+    if (!c) return AM_EINVAL;
+    if (max_bits < 0 || max_bits > 2) return fail(c, AM_EINVAL, "fix_errors: max_bits must be 0, 1 or 2");
+    c->fix_bits = max_bits;
+    return AM_OK;
+}
+int am_get_fix_errors(const am_ctx *c) { return c ? c->fix_bits : AM_EINVAL; }
 
 int am_reset(am_ctx *c)
 {
@@ -1760,7 +1773,8 @@ int am_slicer_work(am_ctx *c, const float *bursts, const am_tag *tags, uint64_t 
     const uint32_t nb32 = (uint32_t)nb;
     HIPCHK(c, hipMemcpyAsync(c->scalars.p, &nb32, sizeof(nb32), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, am_launch_slice((float *)c->bursts.p, (am_tag *)c->tags.p, (const uint32_t *)c->scalars.p, nb32,
-                              (uint32_t *)c->crc_pow.p, (am_packet *)c->packets.p, nullptr, nullptr, c->stream));
+                              (uint32_t *)c->crc_pow.p, (am_packet *)c->packets.p, nullptr, nullptr, c->stream, nullptr,
+                              c->fix_bits));
     c->h_packets.resize(nb);
     HIPCHK(c, hipMemcpyAsync(c->h_packets.data(), c->packets.p, nb * sizeof(am_packet), hipMemcpyDeviceToHost,
                              c->stream));
@@ -2423,6 +2437,17 @@ int am_spipe_set_rx_time(am_spipe *p, uint64_t offset, uint64_t secs, double fra
     return AM_OK;
 }
 
+// (a chunk that has to be redone is sliced again when it is collected: the setting may not change under the chunks in flight)
+int am_spipe_set_fix_errors(am_spipe *p, int max_bits)
+{
+    if (!p) return AM_EINVAL;
+    if (max_bits < 0 || max_bits > 2) return spipe_fail(p, AM_EINVAL, "fix_errors: max_bits must be 0, 1 or 2");
+    if (p->inflight) return spipe_fail(p, AM_EINVAL, "fix_errors: collect the chunks in flight first");
+    for (am_spipe_slot &sl : p->slot) sl.c->fix_bits = max_bits;
+    return AM_OK;
+}
+int am_spipe_get_fix_errors(const am_spipe *p) { return p && !p->slot.empty() ? p->slot[0].c->fix_bits : AM_EINVAL; }
+
 int am_spipe_submit(am_spipe *p, const float *iq, uint64_t n, uint32_t flags)
 {
     if (!p) return AM_EINVAL;
@@ -2605,6 +2630,22 @@ void am_pipe_destroy(am_pipe *p)
 
 int am_pipe_depth(const am_pipe *p) { return p ? (int)p->sub.size() : AM_EINVAL; }
 int am_pipe_in_flight(const am_pipe *p) { return p ? (int)p->inflight : AM_EINVAL; }
+
+// (a batch whose scan met more candidates than it was launched for is scanned and sliced again when it is collected: the
+// setting may not change under the batches in flight)
+int am_pipe_set_fix_errors(am_pipe *p, int max_bits)
+{
+    if (!p) return AM_EINVAL;
+    if (max_bits < 0 || max_bits > 2 || p->inflight) {
+        p->last_fail = nullptr;
+        snprintf(p->err, sizeof(p->err), "%s", p->inflight ? "fix_errors: collect the batches in flight first"
+                                                           : "fix_errors: max_bits must be 0, 1 or 2");
+        return AM_EINVAL;
+    }
+    for (am_ctx *c : p->sub) c->fix_bits = max_bits;
+    return AM_OK;
+}
+int am_pipe_get_fix_errors(const am_pipe *p) { return p && !p->sub.empty() ? p->sub[0]->fix_bits : AM_EINVAL; }
 
 int am_pipe_submit(am_pipe *p, const float *iq, uint64_t n, uint32_t flags)
 {

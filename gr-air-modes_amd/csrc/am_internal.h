@@ -254,7 +254,7 @@ hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc,
                                    uint64_t base_abs, long long e_off, uint64_t rate, const am_time_tag *tt,
                                    uint32_t ntt, float *bursts_out, am_tag *tags_out, const uint32_t *crc_pow,
                                    am_packet *packets, const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                   const uint32_t *Mp = nullptr);
+                                   const uint32_t *Mp, int fix_bits);
 /* the same when bb exists only around the candidates: the burst is recomputed from IQ (iq[0] = absolute sample src_abs0) */
 hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long long src_abs1, int use_pmf, float s1,
                                       const float *inavg, int spc, const uint4 *emit_idx, const uint32_t *n_ptr,
@@ -262,10 +262,13 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
                                       uint64_t rate, const am_time_tag *tt, uint32_t ntt, float *bursts_out,
                                       am_tag *tags_out, const uint32_t *crc_pow, am_packet *packets,
                                       const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                      const uint32_t *Mp = nullptr);
-/* packets[i].reserved[0] = 1 when the reference would post the message, else 0 */
+                                      const uint32_t *Mp, int fix_bits);
+/* packets[i].reserved[0] = 1 when the reference would post the message, else 0.
+ * fix_bits (all three launches; no default: a caller that forgot it would run without the repair and nobody would notice):
+ * which instantiation am_k_*<FIX> runs -- 0 = the kernels as they are without the repair; 1, 2 = DF11 / DF17 replies with up to
+ * that many wrong bits are repaired (am_set_fix_errors) and the number flipped is left in reserved[1] */
 hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const uint32_t *n_ptr, uint32_t n_max,
                            const uint32_t *crc_pow, am_packet *packets, const uint32_t *scalars,
-                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp = nullptr);
+                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits);
 
 #endif

@@ -2122,7 +2122,51 @@ __device__ __forceinline__ bool am_burst_is_long(const float *b)
     return hdr == 16 || hdr == 17 || hdr == 20 || hdr == 21;
 }
 
-// one wave slices burst b (240 soft chips, global memory or LDS); lane 0 files the packet under index i
+// Repair of a DF11 / DF17 reply with one or two wrong bits (am_set_fix_errors).  The reference drops every such
+// reply (slicer_impl.cc:179-182) although modes_packet carries lowconfbits[] "for error correction" (types.h:29-40): the code that
+// was to use them was never written.  Here: the syndrome `part` of an error pattern is the XOR of syn(j) = x^(nbits-1-j) mod G
+// over its bits j (the CRC is linear), and over the positions 5..nbits-1 all one-bit and two-bit patterns have distinct non-zero
+// syndromes, of which no three-bit pattern has one -- so a solution is unique, no search order matters, and three wrong bits are
+// never "repaired" into another frame.  The five DF bits are not candidates: format and length stay what the slicer chose.
+//   one bit:   lane l compares part with syn(l) and syn(l + 64): two compares and two ballots;
+//   two bits:  (DF17 only) for a = 5, 6, ... the lanes compare part ^ syn(a) with their own two syndromes -- at most nbits - 6
+//              wave-uniform turns of a scalar load, two compares and two ballots, ended by the first match (a is then the lower
+//              of the two bits: a match at a lower position would have ended the search in that position's turn).
+// Everything here is wave-uniform but the compares.  Returns the number of bits flipped in m0 / m1 (then part = 0).
+// Known and accepted: a DF11 reply to an all-call with interrogator code 1, 2, 4, ..., 64 carries that code as its syndrome, which
+// is also the syndrome of one wrong bit among the last seven parity bits: with repair on it comes out with crc 0, address intact.
+__device__ __forceinline__ int am_fix_errors(unsigned long long &m0, unsigned long long &m1, uint32_t &part, int nbits, bool two,
+                                             int lane, const uint32_t *__restrict__ crc_pow)
+{
+    // the syndromes of this lane's own two positions (0 = not a candidate: no position's syndrome is zero, and neither is part)
+    const uint32_t s0 = (lane >= 5 && lane < nbits) ? crc_pow[nbits - 1 - lane] : 0u;
+    const uint32_t s1 = (lane + 64 < nbits) ? crc_pow[nbits - 1 - (lane + 64)] : 0u;
+    unsigned long long f0 = __ballot(s0 == part);
+    unsigned long long f1 = __ballot(s1 == part);
+    if (!(f0 | f1) && two) {
+#pragma unroll 1
+        for (int a = 5; a < nbits - 1; ++a) {
+            // (syn(a) read from the lane that holds it -- a v_readlane by a instead of this scalar load -- made the 64 Msps kernel
+            // slower: 45.7-52 against 39.6-49.9 us per launch, profiles/fix_errors/bench_fix.txt)
+            const uint32_t want = part ^ crc_pow[nbits - 1 - a];      // (never 0: syn(a) == part was the one-bit test)
+            f0 = __ballot(s0 == want);
+            f1 = __ballot(s1 == want);
+            if (f0 | f1) {
+                if (a < 64) f0 |= 1ull << a; else f1 |= 1ull << (a - 64);
+                break;
+            }
+        }
+    }
+    if (!(f0 | f1)) return 0;
+    m0 ^= f0;
+    m1 ^= f1;
+    part = 0;
+    return __popcll(f0) + __popcll(f1);
+}
+
+// one wave slices burst b (240 soft chips, global memory or LDS); lane 0 files the packet under index i.
+// FIX: wrong bits to repair (am_fix_errors above): 1 or 2; 0 is the code as it was before the repair existed.
+template <int FIX>
 __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, uint32_t i, int lane,
                                               const uint32_t *__restrict__ crc_pow, am_packet *__restrict__ packets)
 {
@@ -2155,6 +2199,13 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
     if ((m0 >> lane) & 1ull) part ^= crc_pow[nbits - 1 - lane];
     if (lane < 48 && ((m1 >> lane) & 1ull)) part ^= crc_pow[nbits - 1 - (lane + 64)];
     for (int o = 32; o >= 1; o >>= 1) part ^= (uint32_t)__shfl_xor((int)part, o, AM_WAVE);
+    int fixed = 0;
+    if constexpr (FIX > 0) {
+        // only where :182 below would drop the packet: DF11 / DF17 with a bad syndrome that passed :162-171 (DF11 is short and
+        // DF17 long, so :170 never applies; the header bits are set, so :162-166 does not either).  (uniform)
+        if (part != 0 && (hdr == 17 || (hdr == 11 && nlow < 10)))
+            fixed = am_fix_errors(m0, m1, part, nbits, FIX >= 2 && hdr == 17, lane, crc_pow);
+    }
     if (lane == 0) {
         am_packet p;
         for (int k = 0; k < 8; ++k) p.data[k] = (uint8_t)am_bitrev8((uint32_t)((m0 >> (8 * k)) & 0xFFull));
@@ -2168,7 +2219,7 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
         p.df = (uint8_t)mt;
         p.numlowconf = (uint8_t)nlow;
         p.reserved[0] = ok ? 1 : 0;
-        p.reserved[1] = 0;
+        p.reserved[1] = (uint8_t)fixed;                                       // bits repaired (am_set_fix_errors)
         p.reserved[2] = 0;
         p.crc = part;
         p.ref = ref;
@@ -2185,6 +2236,10 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
     }
 }
 
+// (The three slicing kernels are templates over FIX, the number of wrong bits to repair: <0> is what every context launches
+// until am_set_fix_errors turns the repair on, and is instruction for instruction the kernel from before the repair existed:
+// profiles/fix_errors/isa_off_kernels.txt; how to make it again: README.md there.)
+template <int FIX>
 __global__ void __launch_bounds__(256)
 am_k_slice(const float *__restrict__ bursts, const am_tag *__restrict__ tags, const uint32_t *__restrict__ n_ptr,
            const uint32_t *__restrict__ crc_pow, am_packet *__restrict__ packets,
@@ -2200,12 +2255,13 @@ am_k_slice(const float *__restrict__ bursts, const am_tag *__restrict__ tags, co
     }
     if (i >= *n_ptr) return;                              // wave-uniform; device-side burst count
     const am_tag t = tags[i];                             // (lane 0 uses it)
-    am_slice_wave(bursts + (size_t)i * AM_BURST, t, i, lane, crc_pow, packets);
+    am_slice_wave<FIX>(bursts + (size_t)i * AM_BURST, t, i, lane, crc_pow, packets);
 }
 
 // Extraction and slicing in one launch (the scan paths: every extracted burst is sliced right away).  One
 // wave per hit: the 240 soft chips go through LDS instead of a bursts[] round trip through memory; bursts_out
 // and tags_out are written only when the caller wants them (block-level API), packets as am_k_slice does.
+template <int FIX>
 __global__ void __launch_bounds__(256)
 am_k_extract_slice(const float *__restrict__ bb, const float *__restrict__ inavg, int spc,
                    const int *__restrict__ chip_idx, int hist0,
@@ -2242,7 +2298,7 @@ am_k_extract_slice(const float *__restrict__ bb, const float *__restrict__ inavg
     t.how_late = e - pos[g];
     if (tags_out && lane == 0) tags_out[i] = t;
     __builtin_amdgcn_wave_barrier();                       // the wave's own LDS writes, in order, before its reads
-    am_slice_wave(sb[wv], t, i, lane, crc_pow, packets);
+    am_slice_wave<FIX>(sb[wv], t, i, lane, crc_pow, packets);
 }
 
 hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc, const int *chip_idx, int hist0,
@@ -2251,12 +2307,17 @@ hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc,
                                    uint64_t base_abs, long long e_off, uint64_t rate, const am_time_tag *tt,
                                    uint32_t ntt, float *bursts_out, am_tag *tags_out, const uint32_t *crc_pow,
                                    am_packet *packets, const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                   const uint32_t *Mp)
+                                   const uint32_t *Mp, int fix_bits)
 {
     if (n_max == 0) return hipSuccess;
-    hipLaunchKernelGGL(am_k_extract_slice, dim3(am_grid(n_max, 4)), dim3(256), 0, s, bb, inavg, spc, chip_idx, hist0, emit_idx, n_ptr,
-                       pos, e, base_abs, e_off, rate, tt, ntt, bursts_out, tags_out, crc_pow, packets, scalars,
-                       host_out, Mp);
+#define AM_XS(FIX)                                                                                                        \
+    hipLaunchKernelGGL(am_k_extract_slice<FIX>, dim3(am_grid(n_max, 4)), dim3(256), 0, s, bb, inavg, spc, chip_idx, hist0,  \
+                       emit_idx, n_ptr, pos, e, base_abs, e_off, rate, tt, ntt, bursts_out, tags_out, crc_pow, packets,   \
+                       scalars, host_out, Mp)
+    if (fix_bits == 0) AM_XS(0);
+    else if (fix_bits == 1) AM_XS(1);
+    else AM_XS(2);
+#undef AM_XS
     return hipGetLastError();
 }
 
@@ -2433,7 +2494,7 @@ __device__ __forceinline__ float am_soft_chip_row32(const float *E, int row, int
 #ifndef AM_XS_WPS
 #define AM_XS_WPS 8                       /* waves per SIMD the extraction kernel is compiled for (64 VGPRs, no spills: eight workgroups per CU, 2 048 hits in flight) */
 #endif
-template <int SPC>
+template <int SPC, int FIX>
 __global__ void __launch_bounds__(256, AM_XS_WPS)
 am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long long src_abs1, int use_pmf, float s1,
                       const float *__restrict__ inavg, const uint4 *__restrict__ emit_idx,
@@ -2523,7 +2584,7 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
             t.inavg = av;
             t.how_late = e - rec.y;
             if (tags_out && tid == 0) tags_out[i] = t;
-            am_slice_wave(sb, t, i, lane, crc_pow, packets);
+            am_slice_wave<FIX>(sb, t, i, lane, crc_pow, packets);
         }
         __syncthreads();                                          // (sb is rewritten by the next hit)
         AM_XSTAMP(3);
@@ -2544,13 +2605,14 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
                                       uint32_t n_max, const uint32_t *pos, const uint32_t *e, uint64_t base_abs,
                                       uint64_t rate, const am_time_tag *tt, uint32_t ntt, float *bursts_out,
                                       am_tag *tags_out, const uint32_t *crc_pow, am_packet *packets,
-                                      const uint32_t *scalars, uint32_t *host_out, hipStream_t s, const uint32_t *Mp)
+                                      const uint32_t *scalars, uint32_t *host_out, hipStream_t s, const uint32_t *Mp,
+                                      int fix_bits)
 {
     if (n_max == 0) return hipSuccess;
     // workgroups of 256 threads per CU: what the instantiation's registers allow (five at 32 samples per chip, where a lane
     // holds a 34-sample window; eight at one or two samples per chip, where the kernel is a chain of memory round trips per
     // hit and more hits in flight is all that helps), asked of the runtime once per device and instantiation
-    static std::atomic<int> per_cu[64][9];
+    static std::atomic<int> per_cu[64][27];                  // (9 rates x repair of 0, 1, 2 bits)
     int dev = 0;
     (void)hipGetDevice(&dev);
     auto resident_for = [&](const void *kernel, int slot) -> uint32_t {
@@ -2562,13 +2624,19 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
         }
         return (uint32_t)w * (uint32_t)am_device_cus();
     };
-#define AM_XS_IQ(S, SLOT)                                                                                                 \
+#define AM_XS_IQ_F(S, SLOT, FIX)                                                                                          \
     do {                                                                                                                  \
-        const uint32_t resident = resident_for(reinterpret_cast<const void *>(&am_k_extract_slice_iq<S>), SLOT);         \
+        const uint32_t resident = resident_for(reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, FIX>), SLOT + 9 * FIX); \
         const uint32_t grid = n_max < resident ? n_max : resident;                                                        \
-        hipLaunchKernelGGL((am_k_extract_slice_iq<S>), dim3(grid), dim3(256), 0, s, iq, src_abs0, src_abs1, use_pmf, s1, \
+        hipLaunchKernelGGL((am_k_extract_slice_iq<S, FIX>), dim3(grid), dim3(256), 0, s, iq, src_abs0, src_abs1, use_pmf, s1, \
                            inavg, emit_idx, n_ptr, pos, e, base_abs, rate, tt, ntt, bursts_out, tags_out, crc_pow,      \
                            packets, scalars, host_out, Mp);                                                              \
+    } while (0)
+#define AM_XS_IQ(S, SLOT)                                                                                                 \
+    do {                                                                                                                  \
+        if (fix_bits == 0) AM_XS_IQ_F(S, SLOT, 0);                                                                        \
+        else if (fix_bits == 1) AM_XS_IQ_F(S, SLOT, 1);                                                                   \
+        else AM_XS_IQ_F(S, SLOT, 2);                                                                                      \
     } while (0)
     if (spc == 1) use_pmf = 0;                               // (a one-sample window is the sample itself: s1 = 1)
     switch (spc) {                                           // (the rates the streaming front ends serve)
@@ -2584,6 +2652,7 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
     default: return hipErrorInvalidValue;
     }
 #undef AM_XS_IQ
+#undef AM_XS_IQ_F
     return hipGetLastError();
 }
 
@@ -2612,10 +2681,15 @@ hipError_t am_launch_ticket(uint32_t *host_word, uint32_t seq, hipStream_t s, co
 
 hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const uint32_t *n_ptr, uint32_t n_max,
                            const uint32_t *crc_pow, am_packet *packets, const uint32_t *scalars,
-                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp)
+                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits)
 {
     if (n_max == 0) return hipSuccess;
-    hipLaunchKernelGGL(am_k_slice, dim3(am_grid(n_max, 4)), dim3(256), 0, s, bursts, tags, n_ptr, crc_pow, packets,
-                       scalars, host_out, Mp);
+#define AM_SL(FIX)                                                                                                        \
+    hipLaunchKernelGGL(am_k_slice<FIX>, dim3(am_grid(n_max, 4)), dim3(256), 0, s, bursts, tags, n_ptr, crc_pow, packets, scalars, \
+                       host_out, Mp)
+    if (fix_bits == 0) AM_SL(0);
+    else if (fix_bits == 1) AM_SL(1);
+    else AM_SL(2);
+#undef AM_SL
     return hipGetLastError();
 }

@@ -66,7 +66,8 @@ typedef struct am_packet {
     uint8_t  nbytes;       /* 7 = short (56 bit), 14 = long (112 bit)                      */
     uint8_t  df;           /* downlink format = data[0] >> 3  (modes_packet.message_type)  */
     uint8_t  numlowconf;   /* number of low-confidence bits, saturating at 24              */
-    uint8_t  reserved[3];
+    uint8_t  reserved[3];  /* [1]: bits flipped by the opt-in repair (am_set_fix_errors): 0 = as sliced, 1 or 2; then */
+                           /* data holds the repaired bits and crc is 0.  [0], [2]: zero                           */
     uint32_t crc;          /* 24-bit syndrome: crc(data[0..nbytes-3)) ^ last 3 bytes       */
     float    ref;          /* reference_level (mean of the four preamble chips)            */
     uint32_t reserved2;
@@ -136,6 +137,32 @@ AM_API int    am_set_rx_time(am_ctx *ctx, uint64_t offset, uint64_t secs, double
 AM_API double am_get_rate(const am_ctx *ctx);
 AM_API float  am_get_threshold(const am_ctx *ctx);
 AM_API int    am_get_pmf(const am_ctx *ctx);
+/* ---- opt-in repair of DF11 / DF17 replies with one or two wrong bits -------------------------------------------------
+ * Replaces: the drop at lib/slicer_impl.cc:179-182 ("we forget about them") and puts to use what modes_packet's
+ *           lowconfbits[24] / numlowconf were declared for, "for error correction" (include/gr_air_modes/types.h:29-40;
+ *           filled at slicer_impl.cc:157, never read): the reference meant to repair such replies and never did.
+ * max_bits = 0 (default): the reference's behaviour -- every packet, message text and kernel is what it is without this call.
+ * max_bits = 1, 2: a burst is sliced as always (reference level, length from the first five bits, decisions, low-confidence
+ * count, the all-zero test, the two low-confidence drops :162-171, syndrome S :173-177).  Only where :182 drops it -- S != 0
+ * and DF 11 or 17 -- with syn(j) = x^(nbits-1-j) mod G the syndrome of a wrong bit j, candidates j = 5 .. nbits-1 (the five DF
+ * bits are never touched: format and length stay what the slicer chose):
+ *   1. DF11 and DF17: if some a has syn(a) == S, bit a is flipped;
+ *   2. otherwise, max_bits == 2 and DF17 only: if some a < b have syn(a) ^ syn(b) == S, both are flipped;
+ *   3. otherwise the packet is dropped as before.
+ * For 56 and for 112 bits all one-bit and two-bit syndromes are distinct and non-zero and no three-bit pattern shares one, so
+ * the repair is unique when it exists and three wrong bits are never turned into another frame (tests/test_fix_errors.py).
+ * A repaired packet is handed out like any other: data = the repaired bits, crc = 0, reserved[1] = bits flipped (1 or 2),
+ * nbytes, df, numlowconf, ref, sample, secs, frac as the slicer formed them before the repair; am_format_message makes
+ * "<repaired hex> 000000 <level> <secs> <frac>" of it.  Pinned to the reference: its own slicer, given the burst with the two
+ * chips of every repaired bit exchanged (slicer_impl.cc:74-98: the decision flips, the confidence stays), emits that packet.
+ * Known and accepted: a DF11 reply to an all-call with interrogator code 1, 2, 4, ..., 64 carries the code as its syndrome,
+ * which is also that of one wrong bit among the last seven parity bits: with the repair on it comes out with crc 0 (address
+ * intact, interrogator code lost).
+ * The setting belongs to the context, survives am_reset and am_set_rate, takes effect with the next call and covers every
+ * call that slices (am_process_iq / am_process_samples, am_submit_iq, am_process_multi / am_submit_multi, am_slicer_work,
+ * the am_shard_resolve* calls).  AM_EINVAL for max_bits outside 0..2. */
+AM_API int    am_set_fix_errors(am_ctx *ctx, int max_bits);
+AM_API int    am_get_fix_errors(const am_ctx *ctx);
 /* ---- batches in flight ---------------------------------------------------------------------------------------
  * Under GNU Radio every block of rx_path runs in its own thread, so the slicer works on burst k while the preamble
  * block scans ahead (thread-per-block scheduler; python/rx_path.py wires five blocks).  The counterpart here: the
@@ -166,6 +193,10 @@ AM_API int am_pipe_submit_multi(am_pipe *pipe, float *iq, uint32_t k, const uint
 AM_API int am_pipe_multi_counts(am_pipe *pipe, uint64_t *count, uint32_t k);
 AM_API const char *am_pipe_last_error(const am_pipe *pipe);
 AM_API float am_pipe_last_kernel_ms(const am_pipe *pipe);   /* dominant-kernel time of the batch collected last */
+/* Replaces: lib/slicer_impl.cc:179-182 / include/gr_air_modes/types.h:29-40 as am_set_fix_errors, for every context behind
+ * the handle.  AM_EINVAL while batches are in flight (a batch may be sliced again when it is collected). */
+AM_API int am_pipe_set_fix_errors(am_pipe *pipe, int max_bits);
+AM_API int am_pipe_get_fix_errors(const am_pipe *pipe);
 
 /* ---- ONE continuing stream with several of its chunks in flight ---------------------------------------------------
  * The reference's preamble block is a streaming block: general_work() resumes where the last call stopped (lib/preamble_impl.cc:
@@ -198,6 +229,10 @@ AM_API int am_spipe_collect(am_spipe *pipe, am_packet *out, uint64_t cap, uint64
 AM_API uint64_t am_spipe_redone(const am_spipe *pipe);
 AM_API const char *am_spipe_last_error(const am_spipe *pipe);
 AM_API float am_spipe_last_kernel_ms(const am_spipe *pipe);   /* dominant-kernel time of the chunk collected last */
+/* Replaces: lib/slicer_impl.cc:179-182 / include/gr_air_modes/types.h:29-40 as am_set_fix_errors, for the whole stream.
+ * AM_EINVAL while chunks are in flight (as am_spipe_set_rx_time). */
+AM_API int am_spipe_set_fix_errors(am_spipe *pipe, int max_bits);
+AM_API int am_spipe_get_fix_errors(const am_spipe *pipe);
 
 /* Run the context's device work on the caller's HIP stream (hipStream_t passed as a pointer; NULL: back to the
  * context's own stream).  For callers whose input is produced on a stream of their own -- e.g. halo samples that

@@ -170,6 +170,11 @@ class Library(object):
             getattr(L, name).argtypes = [vp, ci]
         for name in ("am_get_fix_errors", "am_pipe_get_fix_errors", "am_spipe_get_fix_errors"):
             getattr(L, name).argtypes = [vp]
+        for name in ("am_set_address_gate", "am_pipe_set_address_gate"):
+            getattr(L, name).argtypes = [vp, ci, f64]
+        for name in ("am_get_address_gate", "am_pipe_get_address_gate"):
+            getattr(L, name).argtypes = [vp, C.POINTER(ci), C.POINTER(f64)]
+        L.am_get_address_gate_stats.argtypes = [vp, pu64, pu64, pu64, pu64]
         self.L = L
         if L.am_abi_version() != ABI_VERSION:
             raise OSError("ABI version mismatch in %s" % path)
@@ -283,6 +288,27 @@ class Context(object):
 
     def get_fix_errors(self):
         return int(self.lib.L.am_get_fix_errors(self._h))
+
+    def set_address_gate(self, mode, ttl=60.0):
+        """Opt-in address gate (am_set_address_gate; 0 = the reference, lib/slicer_impl.cc:170-182): a DF0/4/5/16/20/21 reply is
+        handed out only if a parity-clean DF11 / DF17 reply taught its address at most ttl seconds of samples before it;
+        mode 2 also drops the formats that are neither."""
+        self._chk(self.lib.L.am_set_address_gate(self._h, int(mode), float(ttl)))
+
+    def get_address_gate(self):
+        """(mode, ttl in seconds)"""
+        mode, ttl = C.c_int(0), C.c_double(0.0)
+        self._chk(self.lib.L.am_get_address_gate(self._h, C.byref(mode), C.byref(ttl)))
+        return int(mode.value), float(ttl.value)
+
+    def address_gate_stats(self, not_learned=True):
+        """Since the context was created: dict(taught=, passed=, dropped=, not_learned=) (am_get_address_gate_stats).
+        not_learned=False leaves that one out: it is the only one that has to be fetched from the device."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        p = [C.byref(x) for x in v]
+        self._chk(self.lib.L.am_get_address_gate_stats(self._h, p[0], p[1], p[2], p[3] if not_learned else None))
+        names = ("taught", "passed", "dropped", "not_learned")[:4 if not_learned else 3]
+        return dict(zip(names, (int(x.value) for x in v)))
 
     def reset(self):
         self._chk(self.lib.L.am_reset(self._h))
@@ -692,6 +718,16 @@ class Pipe(object):
 
     def get_fix_errors(self):
         return int(self.lib.L.am_pipe_get_fix_errors(self._h))
+
+    def set_address_gate(self, mode, ttl=60.0):
+        """As Context.set_address_gate, for every context of the pipe (every batch is a whole stream: its own empty map); with
+        no batch in flight."""
+        self._chk(self.lib.L.am_pipe_set_address_gate(self._h, int(mode), float(ttl)))
+
+    def get_address_gate(self):
+        mode, ttl = C.c_int(0), C.c_double(0.0)
+        self._chk(self.lib.L.am_pipe_get_address_gate(self._h, C.byref(mode), C.byref(ttl)))
+        return int(mode.value), float(ttl.value)
 
     def submit(self, iq):
         """A batch in host memory.  The samples must stay valid until the batch is collected: the (possibly converted)

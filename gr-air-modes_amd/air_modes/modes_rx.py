@@ -1,7 +1,7 @@
 """File-source subset of the reference's command-line receiver (apps/modes_rx:32-110,
 python/radio.py:90-118,221-234):
 
-    python -m air_modes.modes_rx -s capture.cf32 -r 2e6 [-T 7.0] [--no-pmf] [--fix-errors N] [-l lat,lon] [-n] [--raw]
+    python -m air_modes.modes_rx -s capture.cf32 -r 2e6 [-T 7.0] [--no-pmf] [--fix-errors N] [--address-gate M] [--address-ttl S] [-l lat,lon] [-n] [--raw]
     python -m air_modes.modes_rx -s rtlsdr.cu8 -r 2.4e6            (-f cu8 when the name does not say it)
 
 Reads a gr_complex file (interleaved little-endian float32 I,Q -- what
@@ -46,6 +46,12 @@ def build_parser():
     ap.add_argument("--fix-errors", type=int, choices=[0, 1, 2], default=0,
                     help="repair DF11 / DF17 replies with up to this many wrong bits (DF17 only for two) instead of "
                     "dropping them as slicer_impl.cc:179-182 does [default=%(default)s]")
+    ap.add_argument("--address-gate", type=int, choices=[0, 1, 2], default=0,
+                    help="believe a DF0/4/5/16/20/21 reply only if a parity-clean DF11 / DF17 reply was heard from its address "
+                    "within --address-ttl (slicer_impl.cc:170-182 checks none of them); 2 also drops reserved formats "
+                    "[default=%(default)s]")
+    ap.add_argument("--address-ttl", type=float, default=60.0, metavar="SECONDS",
+                    help="how long a heard address is believed [default=%(default)s]")
     ap.add_argument("-l", "--location", default=None, help="receiver position as lat,lon (enables range/bearing "
                     "and surface positions)")                                                            # modes_rx:40
     ap.add_argument("-n", "--no-print", action="store_true", help="do not print decoded reports")       # modes_rx:45
@@ -76,7 +82,8 @@ def main(argv=None, out=None):
     if args.rate < 4e6 and not args.no_resample:                      # radio.py:49-53
         # on the GPU, bit-identical to resample.arb_resampler (its definition); the output stays on the device
         rx_rate, resampler = 4e6, resample.gpu_resampler(4e6 / args.rate)
-    rx = rx_path(rx_rate, args.threshold, queue, use_pmf=args.pmf, use_dcblock=args.dcblock, fix_errors=args.fix_errors)
+    rx = rx_path(rx_rate, args.threshold, queue, use_pmf=args.pmf, use_dcblock=args.dcblock, fix_errors=args.fix_errors,
+                 address_gate=args.address_gate, address_ttl=args.address_ttl)    # (below 4 Msps: the window runs at 4 Msps too)
     publisher = pubsub()
     feed = make_parser(publisher)
     my_position = [float(n) for n in args.location.split(",")] if args.location else None

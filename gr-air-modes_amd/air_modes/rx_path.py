@@ -13,7 +13,8 @@ from .blocks import slicer as _slicer
 
 
 class rx_path(object):
-    def __init__(self, rate, threshold, queue, use_pmf=False, use_dcblock=False, device=-1, lib=None, fix_errors=0):
+    def __init__(self, rate, threshold, queue, use_pmf=False, use_dcblock=False, device=-1, lib=None, fix_errors=0,
+                 address_gate=0, address_ttl=60.0):
         self._rate = int(rate)
         self._threshold = threshold
         self._queue = queue
@@ -24,9 +25,13 @@ class rx_path(object):
         self._slicer = _slicer(queue, _ctx=self._ctx)
         self.packets = 0
         self.repaired = 0             # ... of them repaired (set_fix_errors)
+        self._gate_used = False
+        self.gated = 0                # packets the address gate dropped so far (set_address_gate); they are not in `packets`
         self.samples = 0
         if fix_errors:
             self.set_fix_errors(fix_errors)
+        if address_gate:
+            self.set_address_gate(address_gate, address_ttl)
 
     # --- reference surface: python/rx_path.py:67-87 ---
     def set_rate(self, rate):
@@ -55,6 +60,16 @@ class rx_path(object):
 
     def get_fix_errors(self):
         return self._ctx.get_fix_errors()
+
+    # --- beyond the reference: it believes every address/parity reply, whatever its syndrome (lib/slicer_impl.cc:170-182) ---
+    def set_address_gate(self, mode, ttl=60.0):
+        """From the next work() on, hand out a DF0/4/5/16/20/21 reply only if a parity-clean DF11 / DF17 reply taught its address
+        at most ttl seconds of samples before it; mode 2 also drops every other format but 11 and 17 (am_set_address_gate)."""
+        self._ctx.set_address_gate(mode, ttl)
+        self._gate_used = self._gate_used or bool(mode)
+
+    def get_address_gate(self):
+        return self._ctx.get_address_gate()
 
     # --- what the scheduler does for the reference: push samples through ---
     def set_rx_time(self, offset, secs, frac):
@@ -90,6 +105,8 @@ class rx_path(object):
         self._slicer.post(pk)
         self.packets += len(pk)
         self.repaired += int(np.count_nonzero(pk["reserved"][:, 1])) if len(pk) else 0
+        if self._gate_used:
+            self.gated = self._ctx.address_gate_stats(not_learned=False)["dropped"]
         self.samples += int(n)
         return pk
 
@@ -104,10 +121,13 @@ class rx_path_bank(object):
     every receiver carries the six significant digits of a fresh ostringstream, lib/slicer_impl.cc:186-192).  Every call is a set
     of WHOLE streams (item counts and time stamps start at 0): the batch form of rx_path.work(capture, flush=True)."""
 
-    def __init__(self, rate, threshold, queues, use_pmf=False, device=-1, lib=None, fix_errors=0):
+    def __init__(self, rate, threshold, queues, use_pmf=False, device=-1, lib=None, fix_errors=0, address_gate=0,
+                 address_ttl=60.0):
         self._ctx = _capi.Context(float(int(rate)), float(threshold), use_pmf=use_pmf, device=device, lib=lib)
         if fix_errors:
             self._ctx.set_fix_errors(fix_errors)
+        if address_gate:              # every receiver's capture is a stream of its own: a map per receiver
+            self._ctx.set_address_gate(address_gate, address_ttl)
         self._slicers = [_slicer(q, _ctx=self._ctx) for q in queues]
         self.packets = [0] * len(queues)
 

@@ -8,6 +8,7 @@
 #include "am_internal.h"
 
 #include <chrono>
+#include <cmath>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -54,6 +55,17 @@ struct am_ctx {
     float thr_lin = 0.0f;
     int use_pmf = 0;
     int fix_bits = 0;             // am_set_fix_errors: wrong bits a DF11 / DF17 reply may be repaired of (0: none, the reference's :179-182)
+    // am_set_address_gate (kernels: am_gate.inc).  Nothing below is allocated or launched while gate_mode is 0.
+    int gate_mode = 0;            // 0: off; 1: address/parity replies need a taught address; 2: and reserved formats are dropped
+    double gate_ttl_s = 60.0;     // how long a taught address lives, seconds
+    uint64_t gate_ttl = 1;        // ... in item counts: max(1, (uint64)(gate_ttl_s * rate)), formed when a scan is launched
+    DevBuf gate_rec, gate_scratch, gate_map, gate_multi;   // records of the scan, the call's table, the context's map, K streams' limits
+    uint64_t *pin_gate_multi = nullptr;   // pinned staging copy of gate_multi
+    const void *gate_rec_told = nullptr;  // the record array whose address scalars[AM_GATE_REC_WORD] holds
+    bool gate_dirty = false;      // the map has been taught since it was last emptied
+    bool gate_live = false;       // the scan in flight / last collected ran with the gate: pin_scalars[9..11] are its counters
+    am_gate_args ga = {};         // ... and its arguments (am_k_gate_commit gets them again, with the count the host accepted)
+    uint64_t gate_stat[3] = {0, 0, 0};   // taught, passed, dropped since am_create (accepted scans only)
     int tile = 0;
     // Speculative launches: the candidate count of a scan is only known on the device when its kernels
     // are enqueued.  Instead of a host round trip in the middle of the pipeline, the streaming path
@@ -351,6 +363,11 @@ void reset_stream(am_ctx *c)
     c->carry_n = 0;
     c->shard_ready = false;
     c->tt.clear();            // item offsets restart with the stream
+    if (c->gate_dirty) {      // ... and so does what the address gate has learned (the counters in front of the map stay)
+        (void)hipMemsetAsync((unsigned long long *)c->gate_map.p + 4, 0, (size_t)2 * AM_GATE_MAP_SLOTS * sizeof(unsigned long long), c->stream);
+        (void)hipMemsetAsync(c->gate_map.p, 0, sizeof(unsigned long long), c->stream);      // slots taken
+        c->gate_dirty = false;
+    }
     if (c->shard_exit.p) (void)hipMemsetAsync(c->shard_exit.p, 0, 2 * sizeof(uint64_t), c->stream);   // the scan starts at sample 0 again
 }
 
@@ -694,6 +711,76 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
 #endif
 }
 
+// ---- address gate: host side (am_set_address_gate) ----------------------------------------------------------------------
+// Buffers and arguments for the gate over the n_max (or *n_ptr) records the next slicing launch writes: the record array (its
+// address goes into the context's scalar block, where am_slice_wave<FIX, 1> finds it), the call's table, the context's map
+// (zero when allocated) and, for K streams in one scan, their offsets and emit limits.
+int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *packets)
+{
+    am_gate_args &a = c->ga;
+    a = am_gate_args{};
+    if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
+    ENSURE(c, c->gate_rec, (size_t)(n_max ? n_max : 1) * sizeof(am_gate_rec));
+    if (c->gate_rec_told != c->gate_rec.p) {
+        const unsigned long long addr = (unsigned long long)(uintptr_t)c->gate_rec.p;
+        HIPCHK(c, hipMemcpyAsync((uint32_t *)c->scalars.p + AM_GATE_REC_WORD, &addr, sizeof(addr), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));          // (addr is a local; only when the array was (re)allocated)
+        c->gate_rec_told = c->gate_rec.p;
+    }
+    uint32_t slots = 64;
+    while (slots < 2u * n_max) slots <<= 1;                  // (n_max < 2^31 / 240: no overflow)
+    ENSURE(c, c->gate_scratch, am_gate_scratch_bytes(slots));
+    if (!c->gate_map.p) {
+        const size_t bytes = ((size_t)4 + (size_t)2 * AM_GATE_MAP_SLOTS) * sizeof(unsigned long long);
+        ENSURE(c, c->gate_map, bytes);
+        HIPCHK(c, hipMemsetAsync(c->gate_map.p, 0, bytes, c->stream));
+    }
+    am_gate_scratch_layout(a, c->gate_scratch.p, slots);
+    a.rec = (const am_gate_rec *)c->gate_rec.p;
+    a.n_ptr = n_ptr;
+    a.n = n_max;
+    a.hist0 = (unsigned long long)c->geom.hist0;
+    c->gate_ttl = (uint64_t)(c->gate_ttl_s * c->rate);
+    if (c->gate_ttl < 1) c->gate_ttl = 1;
+    a.ttl = c->gate_ttl;
+    a.mode = c->gate_mode;
+    a.t_hdr = (unsigned long long *)c->gate_map.p;
+    a.t_key = a.t_hdr + 4;
+    a.t_last = a.t_key + AM_GATE_MAP_SLOTS;
+    a.t_mask = AM_GATE_MAP_SLOTS - 1u;
+    a.t_limit = (unsigned long long)AM_GATE_MAP_SLOTS / 4 * 3;
+    a.packets = packets;
+    const size_t K = c->multi_off.size();
+    if (K) {
+        // the host sorts the packets into streams only after the scan (sort_into_streams): the gate runs before that and needs the
+        // same table on the device.  Staged through pinned memory, as the streams' time tags are (multi_begin).
+        ENSURE(c, c->gate_multi, (size_t)2 * AM_MAX_TIME_TAGS * sizeof(uint64_t));
+        if (!c->pin_gate_multi)
+            HIPCHK(c, hipHostMalloc((void **)&c->pin_gate_multi, (size_t)2 * AM_MAX_TIME_TAGS * sizeof(uint64_t), hipHostMallocDefault));
+        for (size_t j = 0; j < K; j++) {
+            c->pin_gate_multi[j] = c->multi_off[j];
+            c->pin_gate_multi[K + j] = (uint64_t)c->multi_em[j];
+        }
+        HIPCHK(c, hipMemcpyAsync(c->gate_multi.p, c->pin_gate_multi, 2 * K * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        a.K = (uint32_t)K;
+        a.moff = (const unsigned long long *)c->gate_multi.p;
+        a.mem = (const long long *)c->gate_multi.p + K;
+    }
+    return AM_OK;
+}
+
+// The host has accepted the scan whose records are resident and the stream goes on: its first n records' teaches enter the map.
+int gate_commit(am_ctx *c, uint32_t n)
+{
+    if (!n) return AM_OK;
+    c->ga.n_ptr = nullptr;
+    c->ga.n = n;
+    HIPCHK(c, am_launch_gate_commit(c->ga, c->stream));
+    c->gate_dirty = true;
+    c->tail_synced = false;
+    return AM_OK;
+}
+
 // Greedy chain, part 1 (independent of where the scan starts): successor array and per-block exits
 // over the M flat records (M may be a capacity, with the device-side count in Mp).
 int chain_prepare(am_ctx *c, uint32_t M, bool want_last, const uint32_t *Mp = nullptr)
@@ -728,6 +815,8 @@ int chain_collect(am_ctx *c, uint32_t M, const uint32_t *Mp, uint32_t n_max, boo
     *final_cur = c->pin_scalars[1];
     if (n_emit > n_max) return fail(c, AM_EHIP, "internal: more hits than the spacing bound allows");
     c->n_hits = n_emit;
+    if (c->gate_live)                                        // (an accepted scan: a repeated one returned above)
+        for (int k = 0; k < 3; k++) c->gate_stat[k] += c->pin_scalars[9 + k];
     if (!keep_bursts) {
         const double TC = am_now_us();
         for (uint32_t i = 0; i < n_emit; i++) {
@@ -764,6 +853,7 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
     c->n_hits = 0;
     c->last_M = M;
     c->rec_base = base_abs;
+    c->gate_live = false;
     *final_cur = cur0;
     if (M == 0) return AM_OK;
     const uint32_t nb = (uint32_t)(((uint64_t)M + AM_DET_PER_BLOCK - 1) / AM_DET_PER_BLOCK);
@@ -795,8 +885,12 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
     }
     if (!c->pin_scalars) {
         HIPCHK(c, hipHostMalloc((void **)&c->pin_scalars, 16 * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
-        memset(c->pin_scalars, 0, 16 * sizeof(uint32_t));     // [0..2] results of the slice launch, [3..4] time shards, [5] chained-scan error, [8] completion ticket
+        memset(c->pin_scalars, 0, 16 * sizeof(uint32_t));     // [0..2] results of the slice launch, [3..4] time shards, [5] chained-scan error, [8] completion ticket, [9..11] address gate
     }
+    // the address gate covers the scans that hand out packets (not the block-level preamble, not the time shards, which refuse it)
+    const bool gate = c->gate_mode != 0 && !keep_bursts && !c->resolving_shard && !c->flag_src && !c->word_src;
+    if (gate)
+        if (int rc = gate_prepare(c, n_max, n_ptr, c->pin_packets); rc != AM_OK) return rc;
     // extraction + slicing in one launch; the bursts and their tags leave the kernel only for the block-level
     // caller (am_preamble_work), the accepted packets always land in pinned host memory
     c->pin_scalars[0] = 0;
@@ -815,7 +909,7 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
                                              (uint32_t)c->tt.size(), keep_dev ? (float *)c->bursts.p : nullptr,
                                              keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p,
                                              c->pin_packets, (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp,
-                                             c->fix_bits));
+                                             c->fix_bits, gate ? 1 : 0));
     else
     HIPCHK(c, am_launch_extract_slice(bb, (const float *)c->inavg.p, c->spc, c->frac ? (const int *)c->chip_idx.p : nullptr,
                                       c->geom.hist0, (const uint4 *)c->emit_idx.p, n_ptr, n_max,
@@ -823,14 +917,19 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
                                       (const am_time_tag *)c->tt_dev.p, (uint32_t)c->tt.size(),
                                       keep_dev ? (float *)c->bursts.p : nullptr,
                                       keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p, c->pin_packets,
-                                      (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp, c->fix_bits));
+                                      (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp, c->fix_bits, gate ? 1 : 0));
+    if (gate) HIPCHK(c, am_launch_gate(c->ga, n_max, c->stream));     // behind the slicing launch, in front of the ticket
     if (c->keep_bytes && c->resolving_shard)
         // time shards: the samples the next step needs in front of its chunk, kept while this step's are still in place
         // (am_shard_keep_tail; behind the extraction kernel, which still reads them; complete when the ticket is seen)
         HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
     const uint32_t seq = ++c->ticket_seq;
+    if (gate)
+        HIPCHK(c, am_launch_gate_ticket(c->pin_scalars + 8, seq, c->ga.cnt, c->pin_scalars + 9, c->stream));
+    else
     HIPCHK(c, am_launch_ticket(c->pin_scalars + 8, seq, c->stream, c->flag_src, c->flag_src ? c->pin_scalars + 4 : nullptr,
                                c->word_src, c->word_src ? reinterpret_cast<uint64_t *>(c->pin_scalars + 12) : nullptr));
+    c->gate_live = gate;
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));          // end of the device work of this scan (behind the ticket)
     c->total_pending = true;
     if (c->defer && !keep_bursts) {
@@ -852,6 +951,7 @@ int run_chain_and_slice(am_ctx *c, const float *bb, const float *, uint32_t M, u
     c->h_bursts.clear();
     c->n_hits = 0;
     c->last_M = M;
+    c->gate_live = false;
     *final_cur = cur0;
     int rc = chain_prepare(c, M, false, c->spec_now ? c->Mdev : nullptr);
     if (rc != AM_OK || M == 0) return rc;
@@ -1039,13 +1139,15 @@ void am_destroy(am_ctx *c)
                      &c->energy, &c->bits, &c->seg_base, &c->blk_cnt, &c->blk_off,
                      &c->pos, &c->e, &c->tgt, &c->valid, &c->jump, &c->emit_idx,
                      &c->lb_dc, &c->lb_mark, &c->cblk_cnt, &c->cblk_off, &c->scalars, &c->bursts, &c->tags, &c->packets, &c->crc_pow,
-                     &c->recs, &c->cscratch, &c->dc_m1, &c->dc_y, &c->tt_dev, &c->wgmax, &c->shard_exit, &c->chip_idx};
+                     &c->recs, &c->cscratch, &c->dc_m1, &c->dc_y, &c->tt_dev, &c->wgmax, &c->shard_exit, &c->chip_idx,
+                     &c->gate_rec, &c->gate_scratch, &c->gate_map, &c->gate_multi};
     for (DevBuf *b : all) release(*b);
     if (c->pin_packets) (void)hipHostFree(c->pin_packets);
     if (c->pin_tags) (void)hipHostFree(c->pin_tags);
     if (c->pin_scalars) (void)hipHostFree(c->pin_scalars);
     if (c->pin_exit) (void)hipHostFree(c->pin_exit);
     if (c->pin_tt) (void)hipHostFree(c->pin_tt);
+    if (c->pin_gate_multi) (void)hipHostFree(c->pin_gate_multi);
     for (int i = 0; i < 4; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1144,6 +1246,45 @@ int am_set_fix_errors(am_ctx *c, int max_bits)
     return AM_OK;
 }
 int am_get_fix_errors(const am_ctx *c) { return c ? c->fix_bits : AM_EINVAL; }
+
+// slicer_impl.cc:170-182 checks parity for DF11 / DF17 only: in every other format the syndrome is "the address" and any bit
+// pattern passes.  The setting selects the slicing kernels (am_slice_wave<FIX, GATE>) and the gate launches behind them from the
+// next scan on; the map is kept (the window is formed from ttl and the rate when a scan is launched).
+int am_set_address_gate(am_ctx *c, int mode, double ttl_seconds)
+{
+    if (!c) return AM_EINVAL;
+    if (mode < 0 || mode > 2) return fail(c, AM_EINVAL, "address_gate: mode must be 0, 1 or 2");
+    if (!std::isfinite(ttl_seconds) || !(ttl_seconds > 0.0)) return fail(c, AM_EINVAL, "address_gate: ttl must be finite and positive");
+    c->gate_mode = mode;
+    c->gate_ttl_s = ttl_seconds;
+    return AM_OK;
+}
+int am_get_address_gate(const am_ctx *c, int *mode, double *ttl_seconds)
+{
+    if (!c) return AM_EINVAL;
+    if (mode) *mode = c->gate_mode;
+    if (ttl_seconds) *ttl_seconds = c->gate_ttl_s;
+    return AM_OK;
+}
+// taught / passed / dropped came with the tickets of the accepted scans; not_learned lives in front of the map and is fetched
+// when somebody asks (a wait for the context's stream, here and nowhere else)
+int am_get_address_gate_stats(const am_ctx *c, uint64_t *taught, uint64_t *passed, uint64_t *dropped, uint64_t *not_learned)
+{
+    if (!c) return AM_EINVAL;
+    if (taught) *taught = c->gate_stat[0];
+    if (passed) *passed = c->gate_stat[1];
+    if (dropped) *dropped = c->gate_stat[2];
+    if (not_learned) {
+        unsigned long long v = 0;
+        if (c->gate_map.p) {
+            if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+                hipMemcpy(&v, (const unsigned long long *)c->gate_map.p + 1, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+                return AM_EHIP;
+        }
+        *not_learned = v;
+    }
+    return AM_OK;
+}
 
 int am_reset(am_ctx *c)
 {
@@ -1299,6 +1440,10 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
             rc = run_chain_and_slice(c, bb, avg, M, cur0, emax, out_abs0, false, &fin, max_hits);
         }
         if (rc != AM_OK) return rc;
+        // the scan is the stream's: only now do its teaching replies enter the address gate's map (a scan that was repeated
+        // above has left nothing there).  Not at the end of a stream: the map ends with it (reset_stream below).
+        if (c->gate_live && !flush)
+            if (int grc = gate_commit(c, c->n_hits); grc != AM_OK) return grc;
         c->spec_density = (j1 > j0) ? (double)c->last_M / (double)(j1 - j0) : 0.0;
         c->last_tags = c->n_hits;
         if (out_abs0 + fin > c->chain_cur) c->chain_cur = out_abs0 + fin;
@@ -1772,13 +1917,26 @@ int am_slicer_work(am_ctx *c, const float *bursts, const am_tag *tags, uint64_t 
     if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
     const uint32_t nb32 = (uint32_t)nb;
     HIPCHK(c, hipMemcpyAsync(c->scalars.p, &nb32, sizeof(nb32), hipMemcpyHostToDevice, c->stream));
+    // the address gate on the block alone: the bursts are taken in the order given (item counts ascending, as the preamble block
+    // emits them), nothing is ever repeated, so the call's teaches enter the map right behind its tests
+    const bool gate = c->gate_mode != 0;
+    if (gate)
+        if (int rc = gate_prepare(c, nb32, nullptr, (am_packet *)c->packets.p); rc != AM_OK) return rc;
     HIPCHK(c, am_launch_slice((float *)c->bursts.p, (am_tag *)c->tags.p, (const uint32_t *)c->scalars.p, nb32,
-                              (uint32_t *)c->crc_pow.p, (am_packet *)c->packets.p, nullptr, nullptr, c->stream, nullptr,
-                              c->fix_bits));
+                              (uint32_t *)c->crc_pow.p, (am_packet *)c->packets.p, (const uint32_t *)c->scalars.p, nullptr,
+                              c->stream, nullptr, c->fix_bits, gate ? 1 : 0));
+    unsigned long long gcnt[3] = {0, 0, 0};
+    if (gate) {
+        c->ga.K = 0;                                          // (a layout left by am_submit_multi is not this call's)
+        HIPCHK(c, am_launch_gate(c->ga, nb32, c->stream));
+        if (int rc = gate_commit(c, nb32); rc != AM_OK) return rc;
+        HIPCHK(c, hipMemcpyAsync(gcnt, c->ga.cnt, sizeof(gcnt), hipMemcpyDeviceToHost, c->stream));
+    }
     c->h_packets.resize(nb);
     HIPCHK(c, hipMemcpyAsync(c->h_packets.data(), c->packets.p, nb * sizeof(am_packet), hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; k++) c->gate_stat[k] += gcnt[k];
     c->pending.clear();
     collect_accepted(c);
     return hand_out(c, out, cap, n_out);
@@ -1867,6 +2025,7 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
 {
     if (!c) return AM_EINVAL;
     if (n_table) *n_table = 0;
+    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (abs_end < abs_start || abs_end > total_n) return fail(c, AM_EINVAL, "bad chunk bounds");
     HIPCHK(c, hipSetDevice(c->device));
     c->shard_ready = false;
@@ -2111,6 +2270,7 @@ int am_shard_resolve(am_ctx *c, uint64_t cur_in, am_packet *out, uint64_t cap, u
 {
     if (!c) return AM_EINVAL;
     if (n_out) *n_out = 0;
+    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (!c->shard_ready) return fail(c, AM_EINVAL, "am_shard_scan has not been called");
     HIPCHK(c, hipSetDevice(c->device));
     c->pending.clear();
@@ -2142,6 +2302,7 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
     if (!c || !redo || (world && !msgs_dev) || rank >= world) return AM_EINVAL;
     if (n_out) *n_out = 0;
     *redo = 0;
+    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (!c->shard_ready) return fail(c, AM_EINVAL, "am_shard_scan_async has not been called");
     if (!device_addressable(msgs_dev)) return fail(c, AM_EINVAL, "am_shard_resolve_async: msgs_dev is not device-addressable memory");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2540,6 +2701,7 @@ int am_shard_resolve_submit(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t w
                             const uint64_t *cur_in_dev, uint64_t *carry_out_dev)
 {
     if (!c || (world && !msgs_dev) || rank >= world) return AM_EINVAL;
+    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (!c->shard_ready) return fail(c, AM_EINVAL, "am_shard_scan_async has not been called");
     if (c->pend.active) return fail(c, AM_EINVAL, "a submitted resolve step has not been collected (am_shard_resolve_collect)");
     if (!device_addressable(msgs_dev) || (cur_in_dev && !device_addressable(cur_in_dev)) || (carry_out_dev && !device_addressable(carry_out_dev)))
@@ -2646,6 +2808,26 @@ int am_pipe_set_fix_errors(am_pipe *p, int max_bits)
     return AM_OK;
 }
 int am_pipe_get_fix_errors(const am_pipe *p) { return p && !p->sub.empty() ? p->sub[0]->fix_bits : AM_EINVAL; }
+
+// (every batch is a whole stream: the map of the context that takes it is empty when it starts and is emptied when it ends)
+int am_pipe_set_address_gate(am_pipe *p, int mode, double ttl_seconds)
+{
+    if (!p) return AM_EINVAL;
+    const bool bad = mode < 0 || mode > 2 || !std::isfinite(ttl_seconds) || !(ttl_seconds > 0.0);
+    if (bad || p->inflight) {
+        p->last_fail = nullptr;
+        snprintf(p->err, sizeof(p->err), "%s", bad ? "address_gate: mode must be 0, 1 or 2 and ttl finite and positive"
+                                                   : "address_gate: collect the batches in flight first");
+        return AM_EINVAL;
+    }
+    for (am_ctx *c : p->sub) { c->gate_mode = mode; c->gate_ttl_s = ttl_seconds; }
+    return AM_OK;
+}
+int am_pipe_get_address_gate(const am_pipe *p, int *mode, double *ttl_seconds)
+{
+    if (!p || p->sub.empty()) return AM_EINVAL;
+    return am_get_address_gate(p->sub[0], mode, ttl_seconds);
+}
 
 int am_pipe_submit(am_pipe *p, const float *iq, uint64_t n, uint32_t flags)
 {

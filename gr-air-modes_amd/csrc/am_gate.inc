@@ -1,0 +1,233 @@
+// am_gate.inc -- the address gate (am_set_address_gate; DESIGN.md 14), included by am_kernels.hip.
+//
+// The reference's slicer checks parity for DF11 and DF17 only (lib/slicer_impl.cc:170-182): in DF0/4/5/16/20/21 the parity is
+// overlaid with the aircraft's address, the syndrome IS the address, and every bit pattern "passes".  With the gate on, such a
+// reply is handed out only if its address was taught by a parity-clean DF11 / DF17 reply at most ttl item counts before it.
+//
+// The slicing wave (am_slice_wave<FIX, 1>) leaves one am_gate_rec per hit index in device memory: the packet array is pinned host
+// memory and is never read back here.  Hit indices are in stream order, item counts ascend with them.  The kernels of one call:
+//
+//   (memset)          the call's table and its three counters are zeroed
+//   am_k_gate_teach   every teaching record enters the CALL's table under (stream, address, window), window = item count / ttl:
+//                     first = min item count (kept as max of the complement, so that zero is "none"), last = max item count + 1
+//   am_k_gate_test    a test at item count s in window w passes iff
+//                        the call taught the address in window w before s         (first < s: inside one window every teach is fresh)
+//                     or the call taught it in window w - 1 and s - last <= ttl    (anything in w - 1 is before s; w - 2 is too old)
+//                     or the context's map, taught by EARLIER calls, has it with s - last <= ttl;
+//                     what fails, and with mode 2 every reserved format, loses packets[i].reserved[0] (a byte store to pinned
+//                     memory, as the slicer's own reject)
+//   am_k_gate_ticket  am_k_ticket + the call's three counters for the host
+//
+// and, only once the host has ACCEPTED the scan (a speculative scan that is repeated, or one that timed out, never gets here):
+//
+//   am_k_gate_commit  the call's teaching records enter the context's map: last[address] = max(last, item count + 1)
+//
+// so a repeated scan finds the map as the first try found it, and the call's table is rebuilt from nothing.  Order comes from
+// the launch boundaries on the context's stream alone: integer atomics on 64-bit words, no fences.
+//
+// Both tables are open addressing with linear probing.  The call's table has no keys of its own: a slot is claimed with the
+// index of the first record that hashed there (compare-and-swap on the owner word) and a key is compared by looking that record up,
+// so (stream, address, window) needs no packing into 64 bits.  It has at least twice as many slots as the call can have
+// records, so it never fills.  The context's map holds address + 1; when three quarters of its slots are taken a new address is
+// not learned (the gate fails closed) and a counter says so.
+
+#if defined(__HIP_MEMORY_SCOPE_AGENT)
+#define AM_GATE_SCOPE __HIP_MEMORY_SCOPE_AGENT
+#else
+#define AM_GATE_SCOPE __HIP_MEMORY_SCOPE_SYSTEM
+#endif
+
+__device__ __forceinline__ unsigned long long am_gate_mix(unsigned long long x)
+{
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+// The stream a record belongs to and its item count there (what sort_into_streams does on the host, after the scan); false: the
+// host will drop the packet -- it neither teaches nor counts.  K = 0: one stream, the item count is the record's.
+__device__ __forceinline__ bool am_gate_locate(const am_gate_args &a, unsigned long long raw, uint32_t &j, unsigned long long &s)
+{
+    j = 0;
+    s = raw;
+    if (a.K == 0) return true;
+    const unsigned long long pos = raw - a.hist0;
+    uint32_t lo = 0, hi = a.K;                               // first offset > pos
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (a.moff[mid] <= pos) lo = mid + 1; else hi = mid;
+    }
+    if (lo == 0) return false;
+    j = lo - 1;
+    const unsigned long long e = pos - a.moff[j];
+    if (a.mem[j] < 0 || e > (unsigned long long)a.mem[j]) return false;
+    s = e + a.hist0;
+    return true;
+}
+
+// slot of (j, addr, w) in the call's table, ~0u if it has none; claim = record index + 1: a free slot is taken for it
+__device__ __forceinline__ uint32_t am_gate_slot(const am_gate_args &a, uint32_t j, uint32_t addr, unsigned long long w, uint32_t claim)
+{
+    uint32_t h = (uint32_t)am_gate_mix((((unsigned long long)j << 24) | addr) ^ am_gate_mix(w)) & a.s_mask;
+    for (uint32_t probe = 0; probe <= a.s_mask; ++probe, h = (h + 1) & a.s_mask) {
+        unsigned long long o = __hip_atomic_load(&a.s_owner[h], __ATOMIC_RELAXED, AM_GATE_SCOPE);
+        if (o == 0ull) {
+            if (!claim) return ~0u;
+            unsigned long long expected = 0ull;
+            if (__hip_atomic_compare_exchange_strong(&a.s_owner[h], &expected, (unsigned long long)claim, __ATOMIC_RELAXED,
+                                                     __ATOMIC_RELAXED, AM_GATE_SCOPE))
+                return h;
+            o = expected;                                    // somebody else's record got the slot: is it our key?
+        }
+        const am_gate_rec r = a.rec[o - 1ull];               // (written by the slicing launch; an owner passed am_gate_locate)
+        uint32_t jo;
+        unsigned long long so;
+        (void)am_gate_locate(a, r.sample, jo, so);
+        if (jo == j && r.addr == addr && so / a.ttl == w) return h;
+    }
+    return ~0u;
+}
+
+__global__ void __launch_bounds__(256) am_k_gate_teach(am_gate_args a)
+{
+    const uint32_t n = a.n_ptr ? *a.n_ptr : a.n;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool taught = false;
+    if (i < n) {
+        const am_gate_rec r = a.rec[i];
+        uint32_t j;
+        unsigned long long s;
+        if (r.cls == AM_GC_TEACH && am_gate_locate(a, r.sample, j, s)) {
+            const uint32_t h = am_gate_slot(a, j, r.addr, s / a.ttl, i + 1u);
+            if (h != ~0u) {
+                atomicMax(&a.s_first[h], ~s);
+                atomicMax(&a.s_last[h], s + 1ull);
+            }
+            taught = true;
+        }
+    }
+    const unsigned long long m = __ballot(taught);
+    if ((threadIdx.x & (AM_WAVE - 1)) == 0 && m) atomicAdd(&a.cnt[0], (unsigned long long)__popcll(m));
+}
+
+__global__ void __launch_bounds__(256) am_k_gate_test(am_gate_args a)
+{
+    const uint32_t n = a.n_ptr ? *a.n_ptr : a.n;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool passed = false, dropped = false;
+    if (i < n) {
+        const am_gate_rec r = a.rec[i];
+        uint32_t j;
+        unsigned long long s;
+        if (r.cls >= AM_GC_TEST && am_gate_locate(a, r.sample, j, s)) {
+            bool keep;
+            if (r.cls == AM_GC_OTHER) {
+                keep = a.mode != 2;
+            } else {
+                const unsigned long long w = s / a.ttl;
+                uint32_t h = am_gate_slot(a, j, r.addr, w, 0u);
+                keep = h != ~0u && ~a.s_first[h] < s;
+                if (!keep && w > 0ull) {
+                    h = am_gate_slot(a, j, r.addr, w - 1ull, 0u);
+                    keep = h != ~0u && s - (a.s_last[h] - 1ull) <= a.ttl;
+                }
+                if (!keep) {                                 // the context's map: what earlier calls of this stream taught
+                    uint32_t t = (uint32_t)am_gate_mix(r.addr) & a.t_mask;
+                    for (uint32_t probe = 0; probe <= a.t_mask; ++probe, t = (t + 1) & a.t_mask) {
+                        const unsigned long long k = a.t_key[t];
+                        if (k == 0ull) break;
+                        if (k == (unsigned long long)r.addr + 1ull) {
+                            const unsigned long long l = a.t_last[t];
+                            keep = l != 0ull && l - 1ull <= s && s - (l - 1ull) <= a.ttl;
+                            break;
+                        }
+                    }
+                }
+                passed = keep;
+            }
+            if (!keep) {
+                a.packets[i].reserved[0] = 0;
+                dropped = true;
+            }
+        }
+    }
+    const unsigned long long mp = __ballot(passed), md = __ballot(dropped);
+    if ((threadIdx.x & (AM_WAVE - 1)) == 0) {
+        if (mp) atomicAdd(&a.cnt[1], (unsigned long long)__popcll(mp));
+        if (md) atomicAdd(&a.cnt[2], (unsigned long long)__popcll(md));
+    }
+}
+
+// the teaching records of a scan the host has accepted enter the context's map (one stream: never launched for K streams, whose
+// maps end with the call)
+__global__ void __launch_bounds__(256) am_k_gate_commit(am_gate_args a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const am_gate_rec r = a.rec[i];
+    if (r.cls != AM_GC_TEACH) return;
+    const unsigned long long key = (unsigned long long)r.addr + 1ull;
+    uint32_t t = (uint32_t)am_gate_mix(r.addr) & a.t_mask;
+    for (uint32_t probe = 0; probe <= a.t_mask; ++probe, t = (t + 1) & a.t_mask) {
+        unsigned long long k = __hip_atomic_load(&a.t_key[t], __ATOMIC_RELAXED, AM_GATE_SCOPE);
+        if (k == 0ull) {
+            if (__hip_atomic_load(&a.t_hdr[0], __ATOMIC_RELAXED, AM_GATE_SCOPE) >= a.t_limit) break;    // full: not learned
+            unsigned long long expected = 0ull;
+            if (__hip_atomic_compare_exchange_strong(&a.t_key[t], &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, AM_GATE_SCOPE)) {
+                atomicAdd(&a.t_hdr[0], 1ull);
+                k = key;
+            } else {
+                k = expected;
+            }
+        }
+        if (k == key) {
+            atomicMax(&a.t_last[t], r.sample + 1ull);
+            return;
+        }
+    }
+    atomicAdd(&a.t_hdr[1], 1ull);
+}
+
+// am_k_ticket for a scan with the gate: the call's counters (taught, passed, dropped) travel with the ticket
+__global__ void am_k_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, uint32_t *cnt_dst)
+{
+    cnt_dst[0] = (uint32_t)cnt[0];
+    cnt_dst[1] = (uint32_t)cnt[1];
+    cnt_dst[2] = (uint32_t)cnt[2];
+    __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+size_t am_gate_scratch_bytes(uint32_t slots) { return ((size_t)4 + (size_t)3 * slots) * sizeof(unsigned long long); }
+
+void am_gate_scratch_layout(am_gate_args &a, void *scratch, uint32_t slots)
+{
+    unsigned long long *p = static_cast<unsigned long long *>(scratch);
+    a.cnt = p;
+    a.s_owner = p + 4;
+    a.s_first = p + 4 + (size_t)slots;
+    a.s_last = p + 4 + (size_t)2 * slots;
+    a.s_mask = slots - 1u;
+}
+
+hipError_t am_launch_gate(const am_gate_args &a, uint32_t n_max, hipStream_t s)
+{
+    hipError_t rc = hipMemsetAsync(a.cnt, 0, am_gate_scratch_bytes(a.s_mask + 1u), s);
+    if (rc != hipSuccess || n_max == 0) return rc;
+    hipLaunchKernelGGL(am_k_gate_teach, dim3(am_grid(n_max, 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(am_k_gate_test, dim3(am_grid(n_max, 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t am_launch_gate_commit(const am_gate_args &a, hipStream_t s)
+{
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(am_k_gate_commit, dim3(am_grid(a.n, 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t am_launch_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, uint32_t *cnt_dst, hipStream_t s)
+{
+    hipLaunchKernelGGL(am_k_gate_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, cnt_dst);
+    return hipGetLastError();
+}

@@ -254,7 +254,7 @@ hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc,
                                    uint64_t base_abs, long long e_off, uint64_t rate, const am_time_tag *tt,
                                    uint32_t ntt, float *bursts_out, am_tag *tags_out, const uint32_t *crc_pow,
                                    am_packet *packets, const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                   const uint32_t *Mp, int fix_bits);
+                                   const uint32_t *Mp, int fix_bits, int gate);
 /* the same when bb exists only around the candidates: the burst is recomputed from IQ (iq[0] = absolute sample src_abs0) */
 hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long long src_abs1, int use_pmf, float s1,
                                       const float *inavg, int spc, const uint4 *emit_idx, const uint32_t *n_ptr,
@@ -262,13 +262,55 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
                                       uint64_t rate, const am_time_tag *tt, uint32_t ntt, float *bursts_out,
                                       am_tag *tags_out, const uint32_t *crc_pow, am_packet *packets,
                                       const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                      const uint32_t *Mp, int fix_bits);
+                                      const uint32_t *Mp, int fix_bits, int gate);
+/* ---- address gate (am_set_address_gate; am_gate.inc) ----------------------------------------------------
+ * One record per hit index, written by lane 0 of the slicing wave (am_slice_wave<FIX, 1>) into DEVICE memory: the packet
+ * array is pinned host memory, which a kernel does not read back. */
+struct am_gate_rec {
+    unsigned long long sample;   /* am_packet.sample (for K streams: still in the coordinates of the scanned buffer)          */
+    uint32_t addr;               /* teach: data[1..3], big-endian; test: the syndrome                                         */
+    uint32_t cls;                /* AM_GC_*                                                                                   */
+};
+#define AM_GC_NONE 0u    /* rejected by the slicer, or kept without a part in the gate (a repaired DF11 / DF17 reply)          */
+#define AM_GC_TEACH 1u   /* DF11 / DF17, syndrome 0 as sliced: teaches its address, kept                                       */
+#define AM_GC_TEST 2u    /* DF0/4/5/16/20/21: kept iff the address was taught at most ttl item counts before                   */
+#define AM_GC_OTHER 3u   /* any other format: mode 1 keeps it, mode 2 drops it                                                 */
+#define AM_GATE_REC_WORD 14   /* scalars[14..15] of the context's device block: the address of the record array               */
+#define AM_GATE_MAP_SLOTS (1u << 18)   /* the context's map; three quarters may be taken: 196 608 addresses alive               */
+struct am_gate_args {
+    const am_gate_rec *rec;
+    const uint32_t *n_ptr;               /* device-side record count, or null: n                                               */
+    uint32_t n;
+    uint32_t K;                          /* streams in the scan (am_process_multi), 0: one                                      */
+    const unsigned long long *moff;      /* [K] where stream j starts in the scanned buffer                                     */
+    const long long *mem;                /* [K] the last position it may emit, -1: none                                         */
+    unsigned long long hist0;
+    unsigned long long ttl;              /* window in item counts, >= 1                                                         */
+    int mode;
+    unsigned long long *cnt;             /* the call's table: [0] taught [1] passed [2] dropped, then owner / first / last      */
+    unsigned long long *s_owner, *s_first, *s_last;
+    uint32_t s_mask;
+    unsigned long long *t_hdr;           /* the context's map: [0] slots taken, [1] addresses not learned                       */
+    unsigned long long *t_key, *t_last;
+    uint32_t t_mask;
+    unsigned long long t_limit;
+    am_packet *packets;
+};
+size_t am_gate_scratch_bytes(uint32_t slots);                                   /* slots: a power of two                      */
+void am_gate_scratch_layout(am_gate_args &a, void *scratch, uint32_t slots);
+hipError_t am_launch_gate(const am_gate_args &a, uint32_t n_max, hipStream_t s);   /* zero the call's table, teach, test     */
+hipError_t am_launch_gate_commit(const am_gate_args &a, hipStream_t s);            /* a.n records of an ACCEPTED scan         */
+hipError_t am_launch_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, uint32_t *cnt_dst,
+                                 hipStream_t s);
+
 /* packets[i].reserved[0] = 1 when the reference would post the message, else 0.
  * fix_bits (all three launches; no default: a caller that forgot it would run without the repair and nobody would notice):
  * which instantiation am_k_*<FIX> runs -- 0 = the kernels as they are without the repair; 1, 2 = DF11 / DF17 replies with up to
- * that many wrong bits are repaired (am_set_fix_errors) and the number flipped is left in reserved[1] */
+ * that many wrong bits are repaired (am_set_fix_errors) and the number flipped is left in reserved[1].
+ * gate (likewise): 1 = am_k_*<FIX, 1>, which also leaves an am_gate_rec per hit at the address in scalars[AM_GATE_REC_WORD]
+ * (scalars must not be null then); 0 = the kernels as they are without the gate */
 hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const uint32_t *n_ptr, uint32_t n_max,
                            const uint32_t *crc_pow, am_packet *packets, const uint32_t *scalars,
-                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits);
+                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits, int gate);
 
 #endif

@@ -2166,9 +2166,13 @@ __device__ __forceinline__ int am_fix_errors(unsigned long long &m0, unsigned lo
 
 // one wave slices burst b (240 soft chips, global memory or LDS); lane 0 files the packet under index i.
 // FIX: wrong bits to repair (am_fix_errors above): 1 or 2; 0 is the code as it was before the repair existed.
-template <int FIX>
+// GATE: 1 = lane 0 also files the hit's part in the address gate (am_gate.inc) as record i of the array whose address the
+// context keeps in scalars[AM_GATE_REC_WORD] (device memory; a kernel argument of its own would change the <FIX, 0> kernels'
+// descriptors); 0 is the code as it was before the gate existed, and never looks at scalars.
+template <int FIX, int GATE>
 __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, uint32_t i, int lane,
-                                              const uint32_t *__restrict__ crc_pow, am_packet *__restrict__ packets)
+                                              const uint32_t *__restrict__ crc_pow, am_packet *__restrict__ packets,
+                                              const uint32_t *__restrict__ scalars)
 {
     float s = b[0] + b[2];                                // slicer_impl.cc:128-131
     s = s + b[7];
@@ -2224,6 +2228,26 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
         p.crc = part;
         p.ref = ref;
         p.reserved2 = 0;
+        if constexpr (GATE > 0) {
+            am_gate_rec r;
+            r.sample = t.sample;
+            r.addr = part;
+            r.cls = AM_GC_NONE;
+            if (ok) {
+                if (mt == 11 || mt == 17) {                                   // (ok: the syndrome is 0, as sliced or repaired)
+                    if (!fixed) {
+                        r.cls = AM_GC_TEACH;
+                        r.addr = ((uint32_t)p.data[1] << 16) | ((uint32_t)p.data[2] << 8) | (uint32_t)p.data[3];
+                    }
+                } else if (mt == 0 || mt == 4 || mt == 5 || mt == 16 || mt == 20 || mt == 21) {
+                    r.cls = AM_GC_TEST;
+                } else {
+                    r.cls = AM_GC_OTHER;
+                }
+            }
+            am_gate_rec *grec = *reinterpret_cast<am_gate_rec *const *>(scalars + AM_GATE_REC_WORD);
+            grec[i] = r;
+        }
         if (!ok) {
             // never handed out: only the flag travels (the packet array is usually pinned host memory)
             packets[i].reserved[0] = 0;
@@ -2238,8 +2262,10 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
 
 // (The three slicing kernels are templates over FIX, the number of wrong bits to repair: <0> is what every context launches
 // until am_set_fix_errors turns the repair on, and is instruction for instruction the kernel from before the repair existed:
-// profiles/fix_errors/isa_off_kernels.txt; how to make it again: README.md there.)
-template <int FIX>
+// profiles/fix_errors/isa_off_kernels.txt; how to make it again: README.md there.  Likewise GATE, the address gate
+// (am_set_address_gate): <FIX, 0> is instruction for instruction the kernel <FIX> from before the gate existed:
+// profiles/address_gate/isa_off_kernels.txt.)
+template <int FIX, int GATE>
 __global__ void __launch_bounds__(256)
 am_k_slice(const float *__restrict__ bursts, const am_tag *__restrict__ tags, const uint32_t *__restrict__ n_ptr,
            const uint32_t *__restrict__ crc_pow, am_packet *__restrict__ packets,
@@ -2255,13 +2281,13 @@ am_k_slice(const float *__restrict__ bursts, const am_tag *__restrict__ tags, co
     }
     if (i >= *n_ptr) return;                              // wave-uniform; device-side burst count
     const am_tag t = tags[i];                             // (lane 0 uses it)
-    am_slice_wave<FIX>(bursts + (size_t)i * AM_BURST, t, i, lane, crc_pow, packets);
+    am_slice_wave<FIX, GATE>(bursts + (size_t)i * AM_BURST, t, i, lane, crc_pow, packets, scalars);
 }
 
 // Extraction and slicing in one launch (the scan paths: every extracted burst is sliced right away).  One
 // wave per hit: the 240 soft chips go through LDS instead of a bursts[] round trip through memory; bursts_out
 // and tags_out are written only when the caller wants them (block-level API), packets as am_k_slice does.
-template <int FIX>
+template <int FIX, int GATE>
 __global__ void __launch_bounds__(256)
 am_k_extract_slice(const float *__restrict__ bb, const float *__restrict__ inavg, int spc,
                    const int *__restrict__ chip_idx, int hist0,
@@ -2298,7 +2324,7 @@ am_k_extract_slice(const float *__restrict__ bb, const float *__restrict__ inavg
     t.how_late = e - pos[g];
     if (tags_out && lane == 0) tags_out[i] = t;
     __builtin_amdgcn_wave_barrier();                       // the wave's own LDS writes, in order, before its reads
-    am_slice_wave<FIX>(sb[wv], t, i, lane, crc_pow, packets);
+    am_slice_wave<FIX, GATE>(sb[wv], t, i, lane, crc_pow, packets, scalars);
 }
 
 hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc, const int *chip_idx, int hist0,
@@ -2307,17 +2333,20 @@ hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc,
                                    uint64_t base_abs, long long e_off, uint64_t rate, const am_time_tag *tt,
                                    uint32_t ntt, float *bursts_out, am_tag *tags_out, const uint32_t *crc_pow,
                                    am_packet *packets, const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                   const uint32_t *Mp, int fix_bits)
+                                   const uint32_t *Mp, int fix_bits, int gate)
 {
     if (n_max == 0) return hipSuccess;
-#define AM_XS(FIX)                                                                                                        \
-    hipLaunchKernelGGL(am_k_extract_slice<FIX>, dim3(am_grid(n_max, 4)), dim3(256), 0, s, bb, inavg, spc, chip_idx, hist0,  \
+#define AM_XS_G(FIX, GATE)                                                                                                \
+    hipLaunchKernelGGL((am_k_extract_slice<FIX, GATE>), dim3(am_grid(n_max, 4)), dim3(256), 0, s, bb, inavg, spc, chip_idx, hist0,  \
                        emit_idx, n_ptr, pos, e, base_abs, e_off, rate, tt, ntt, bursts_out, tags_out, crc_pow, packets,   \
                        scalars, host_out, Mp)
+#define AM_XS(FIX)                                                                                                        \
+    do { if (gate) AM_XS_G(FIX, 1); else AM_XS_G(FIX, 0); } while (0)
     if (fix_bits == 0) AM_XS(0);
     else if (fix_bits == 1) AM_XS(1);
     else AM_XS(2);
 #undef AM_XS
+#undef AM_XS_G
     return hipGetLastError();
 }
 
@@ -2494,7 +2523,7 @@ __device__ __forceinline__ float am_soft_chip_row32(const float *E, int row, int
 #ifndef AM_XS_WPS
 #define AM_XS_WPS 8                       /* waves per SIMD the extraction kernel is compiled for (64 VGPRs, no spills: eight workgroups per CU, 2 048 hits in flight) */
 #endif
-template <int SPC, int FIX>
+template <int SPC, int FIX, int GATE>
 __global__ void __launch_bounds__(256, AM_XS_WPS)
 am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long long src_abs1, int use_pmf, float s1,
                       const float *__restrict__ inavg, const uint4 *__restrict__ emit_idx,
@@ -2584,7 +2613,7 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
             t.inavg = av;
             t.how_late = e - rec.y;
             if (tags_out && tid == 0) tags_out[i] = t;
-            am_slice_wave<FIX>(sb, t, i, lane, crc_pow, packets);
+            am_slice_wave<FIX, GATE>(sb, t, i, lane, crc_pow, packets, scalars);
         }
         __syncthreads();                                          // (sb is rewritten by the next hit)
         AM_XSTAMP(3);
@@ -2606,13 +2635,13 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
                                       uint64_t rate, const am_time_tag *tt, uint32_t ntt, float *bursts_out,
                                       am_tag *tags_out, const uint32_t *crc_pow, am_packet *packets,
                                       const uint32_t *scalars, uint32_t *host_out, hipStream_t s, const uint32_t *Mp,
-                                      int fix_bits)
+                                      int fix_bits, int gate)
 {
     if (n_max == 0) return hipSuccess;
     // workgroups of 256 threads per CU: what the instantiation's registers allow (five at 32 samples per chip, where a lane
     // holds a 34-sample window; eight at one or two samples per chip, where the kernel is a chain of memory round trips per
     // hit and more hits in flight is all that helps), asked of the runtime once per device and instantiation
-    static std::atomic<int> per_cu[64][27];                  // (9 rates x repair of 0, 1, 2 bits)
+    static std::atomic<int> per_cu[64][54];                  // (9 rates x repair of 0, 1, 2 bits x address gate off, on)
     int dev = 0;
     (void)hipGetDevice(&dev);
     auto resident_for = [&](const void *kernel, int slot) -> uint32_t {
@@ -2624,14 +2653,16 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
         }
         return (uint32_t)w * (uint32_t)am_device_cus();
     };
-#define AM_XS_IQ_F(S, SLOT, FIX)                                                                                          \
+#define AM_XS_IQ_G(S, SLOT, FIX, GATE)                                                                                    \
     do {                                                                                                                  \
-        const uint32_t resident = resident_for(reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, FIX>), SLOT + 9 * FIX); \
+        const uint32_t resident = resident_for(reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, FIX, GATE>), SLOT + 9 * FIX + 27 * GATE); \
         const uint32_t grid = n_max < resident ? n_max : resident;                                                        \
-        hipLaunchKernelGGL((am_k_extract_slice_iq<S, FIX>), dim3(grid), dim3(256), 0, s, iq, src_abs0, src_abs1, use_pmf, s1, \
+        hipLaunchKernelGGL((am_k_extract_slice_iq<S, FIX, GATE>), dim3(grid), dim3(256), 0, s, iq, src_abs0, src_abs1, use_pmf, s1, \
                            inavg, emit_idx, n_ptr, pos, e, base_abs, rate, tt, ntt, bursts_out, tags_out, crc_pow,      \
                            packets, scalars, host_out, Mp);                                                              \
     } while (0)
+#define AM_XS_IQ_F(S, SLOT, FIX)                                                                                          \
+    do { if (gate) AM_XS_IQ_G(S, SLOT, FIX, 1); else AM_XS_IQ_G(S, SLOT, FIX, 0); } while (0)
 #define AM_XS_IQ(S, SLOT)                                                                                                 \
     do {                                                                                                                  \
         if (fix_bits == 0) AM_XS_IQ_F(S, SLOT, 0);                                                                        \
@@ -2653,6 +2684,7 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
     }
 #undef AM_XS_IQ
 #undef AM_XS_IQ_F
+#undef AM_XS_IQ_G
     return hipGetLastError();
 }
 
@@ -2681,15 +2713,20 @@ hipError_t am_launch_ticket(uint32_t *host_word, uint32_t seq, hipStream_t s, co
 
 hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const uint32_t *n_ptr, uint32_t n_max,
                            const uint32_t *crc_pow, am_packet *packets, const uint32_t *scalars,
-                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits)
+                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits, int gate)
 {
     if (n_max == 0) return hipSuccess;
-#define AM_SL(FIX)                                                                                                        \
-    hipLaunchKernelGGL(am_k_slice<FIX>, dim3(am_grid(n_max, 4)), dim3(256), 0, s, bursts, tags, n_ptr, crc_pow, packets, scalars, \
+#define AM_SL_G(FIX, GATE)                                                                                                \
+    hipLaunchKernelGGL((am_k_slice<FIX, GATE>), dim3(am_grid(n_max, 4)), dim3(256), 0, s, bursts, tags, n_ptr, crc_pow, packets, scalars, \
                        host_out, Mp)
+#define AM_SL(FIX)                                                                                                        \
+    do { if (gate) AM_SL_G(FIX, 1); else AM_SL_G(FIX, 0); } while (0)
     if (fix_bits == 0) AM_SL(0);
     else if (fix_bits == 1) AM_SL(1);
     else AM_SL(2);
 #undef AM_SL
+#undef AM_SL_G
     return hipGetLastError();
 }
+
+#include "am_gate.inc"

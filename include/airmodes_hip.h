@@ -43,7 +43,7 @@ extern "C" {
 #define AM_ENOMEM     (-3)   /* host or device allocation failed                            */
 #define AM_EHIP       (-4)   /* a HIP runtime call failed (see am_last_error)               */
 #define AM_ECAPACITY  (-5)   /* output did not fit; *n_out holds the required count         */
-#define AM_ENOTSUP    (-6)   /* option not implemented (none at present)                    */
+#define AM_ENOTSUP    (-6)   /* option not implemented (time shards with the address gate)  */
 
 /* flags for the *_work / am_process_iq calls */
 #define AM_F_DEVICE_IN  0x1u  /* input pointers are device memory on the context's GPU      */
@@ -163,6 +163,42 @@ AM_API int    am_get_pmf(const am_ctx *ctx);
  * the am_shard_resolve* calls).  AM_EINVAL for max_bits outside 0..2. */
 AM_API int    am_set_fix_errors(am_ctx *ctx, int max_bits);
 AM_API int    am_get_fix_errors(const am_ctx *ctx);
+/* ---- opt-in address gate for address/parity replies (DF0/4/5/16/20/21) ------------------------------------------------
+ * Replaces: lib/slicer_impl.cc:170-182, which checks parity for DF11 and DF17 only.  In every other format the 24 parity
+ *           bits are overlaid with the aircraft's address, so the syndrome handed on as "ecc" IS the address and any bit
+ *           pattern passes (:170 filters only the short ones by confidence): a false preamble whose first five bits slice to
+ *           16, 20 or 21 becomes a fictitious aircraft, a real reply with one wrong bit a reply of the wrong aircraft.
+ * mode = 0 (default): the reference's behaviour -- every packet, message text and kernel is what it is without this call.
+ * mode = 1, 2: the packets of a stream are formed exactly as always (all drops of :162-182, the repair if it is on).  Then, in
+ * stream order, with a map last[address] -> item count that is empty when a stream starts, for a packet p at item count
+ * s = p.sample and ttl_samples = max(1, (uint64)(ttl_seconds * rate)):
+ *   1. teach:  p.df is 11 or 17, p.crc == 0 and p.reserved[1] == 0 (as sliced, not repaired):
+ *              last[data[1..3], big-endian] = s.  The packet is kept.  (A repaired DF11 / DF17 packet is kept and teaches nothing.)
+ *   2. test:   p.df in {0, 4, 5, 16, 20, 21}: kept iff last[p.crc] exists and s - last[p.crc] <= ttl_samples.  A kept reply does
+ *              not teach: noise must not be able to keep itself alive.
+ *   3. others: DF1-3, 6-10, 12-15, 18, 19, 22-31 (reserved formats, and 18 / 19 / 24.., which are long on the air but which
+ *              :140 slices as 56 bits): mode 1 keeps them, mode 2 drops them.
+ * A dropped packet is simply not handed out; a kept one is byte for byte what it is with the gate off.  Item counts are used,
+ * not secs / frac: "rx_time" tags do not move the window.  The result does not depend on how the stream is cut into calls,
+ * and the packets with the gate on are a subsequence of those with it off (tests/gate_common.py restates this in numpy).
+ * am_reset, am_set_rate and AM_F_FLUSH empty the map (item counts restart); the setting survives them.  A new mode or ttl takes
+ * effect with the next call and keeps the map.  The map holds 196 608 addresses; one that does not fit is not learned (the gate
+ * fails closed) and not_learned counts it.  Only parity-clean replies teach: noise enters at 2^-24 per false DF11 / DF17.
+ * Covered: am_process_iq / am_process_samples (any chunking, AM_F_DEVICE_IN or not, AM_ECAPACITY + am_fetch_packets),
+ * am_submit_iq / am_collect and am_pipe_* (every batch is a whole stream with a map of its own), am_process_multi /
+ * am_submit_multi / am_pipe_submit_multi (stream j of the K has a map of its own), am_slicer_work (the block alone: bursts in
+ * ascending item counts; the context's map carries over from call to call until am_reset).  am_fetch_tags / am_last_num_tags
+ * are about preamble hits and do not change.
+ * NOT covered: am_spipe_* (chunks of one stream in flight on several contexts; no setter) and the time shards (the map would
+ * have to cross ranks): with the gate on, am_shard_scan* / am_shard_resolve* return AM_ENOTSUP.
+ * AM_EINVAL: mode outside 0..2, ttl_seconds not finite or <= 0.
+ * Stats: since am_create, over all streams, of scans the library accepted (a speculative scan that had to be repeated counts
+ * once): replies that taught, address/parity replies kept, packets dropped by the gate, addresses not learned.  Any pointer
+ * may be null; asking for not_learned waits for the context's stream. */
+AM_API int    am_set_address_gate(am_ctx *ctx, int mode, double ttl_seconds);
+AM_API int    am_get_address_gate(const am_ctx *ctx, int *mode, double *ttl_seconds);
+AM_API int    am_get_address_gate_stats(const am_ctx *ctx, uint64_t *taught, uint64_t *passed, uint64_t *dropped,
+                                        uint64_t *not_learned);
 /* ---- batches in flight ---------------------------------------------------------------------------------------
  * Under GNU Radio every block of rx_path runs in its own thread, so the slicer works on burst k while the preamble
  * block scans ahead (thread-per-block scheduler; python/rx_path.py wires five blocks).  The counterpart here: the
@@ -197,6 +233,10 @@ AM_API float am_pipe_last_kernel_ms(const am_pipe *pipe);   /* dominant-kernel t
  * the handle.  AM_EINVAL while batches are in flight (a batch may be sliced again when it is collected). */
 AM_API int am_pipe_set_fix_errors(am_pipe *pipe, int max_bits);
 AM_API int am_pipe_get_fix_errors(const am_pipe *pipe);
+/* Replaces: lib/slicer_impl.cc:170-182 as am_set_address_gate, for every context behind the handle (every batch is a whole
+ * stream: its own empty map).  AM_EINVAL while batches are in flight, and for what am_set_address_gate refuses. */
+AM_API int am_pipe_set_address_gate(am_pipe *pipe, int mode, double ttl_seconds);
+AM_API int am_pipe_get_address_gate(const am_pipe *pipe, int *mode, double *ttl_seconds);
 
 /* ---- ONE continuing stream with several of its chunks in flight ---------------------------------------------------
  * The reference's preamble block is a streaming block: general_work() resumes where the last call stopped (lib/preamble_impl.cc:

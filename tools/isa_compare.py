@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Are the slicing kernels a build launches with the repair off the kernels of another build (the parent commit's)?
+"""Are the slicing kernels a build launches with its newest option off the kernels of another build (the parent commit's)?
 
 Two gfx950 assembly listings of csrc/am_kernels.hip, made with the Makefile's flags plus `--cuda-device-only -S`:
     python tools/isa_compare.py parent.s this.s
 Every kernel whose name contains "slice" is compared as its instruction stream AND its kernel descriptor (.amdhsa_* block:
 registers, LDS, scratch, kernarg size), comments stripped, basic-block labels renumbered per function and the kernel's own
 mangled name replaced by a placeholder.  A kernel `name<..., 0>` of the second listing is matched with `name<...>` of the
-first (the template argument FIX = 0 is the only difference in the name).  Exit status 1 if any pair differs."""
+first: the last template argument, = 0, is the only difference in the name (FIX when the repair was added, GATE when the
+address gate was: `am_k_extract_slice_iq<32, 1, 0>` is matched with `am_k_extract_slice_iq<32, 1>`).  Exit status 1 if any pair differs."""
 import re
 import subprocess
 import sys
@@ -48,9 +49,9 @@ def main():
     for k, d in sorted(nb.items(), key=lambda kv: kv[1]):
         lines, info = b[k]
         text = "%-36s %5d lines  %s" % (d, len(lines), " ".join("%s=%s" % kv for kv in info.items()))
-        m = re.match(r"(\w+)<(?:(\d+), )?0>$", d)
+        m = re.match(r"(\w+)<((?:\d+, )*)0>$", d)
         if m:
-            old = m.group(1) + ("<%s>" % m.group(2) if m.group(2) else "")
+            old = m.group(1) + ("<%s>" % m.group(2)[:-2] if m.group(2) else "")
             same = old in first and a[first[old]][0] == lines and a[first[old]][1] == info
             text += "   == %s of the first listing: %s" % (old, "IDENTICAL" if same else "DIFFERENT")
             worst |= not same

@@ -768,14 +768,17 @@ def check_framer_edge_formats(lib, rate, n, lam, seed, want_fe=None):
 
 
 def check_stream_pipe(lib, rate, n, lam, seed, depth=3, thr=7.0, pmf=True, dcblock=False, contiguous=True, min_chunk=None, rx_time=None,
-                      device=None):
+                      device=None, iq=None):
     """ONE continuing stream with `depth` consecutive chunks in flight (am_spipe: VERDICT r5 #3, lib/preamble_impl.cc:139-246 is a
     streaming block): random chunk sizes; the stream contiguous in memory, or every chunk in a buffer of its own with room for the
     previous chunk's tail in front of it; packets of all chunks == the oracle over the WHOLE stream (item counts and time stamps
     continue), == am_process_iq over the same cuts.  device: a torch device (the chunks then live in device memory); None: the
-    emulation, where device memory is host memory.  Returns (packets, chunks redone on the synchronous path)."""
+    emulation, where device memory is host memory.  iq: this stream instead of the seeded capture (n, lam are then unused).  Returns
+    (packets, chunks redone on the synchronous path)."""
     rng = np.random.default_rng(seed)
-    iq, _ = synth.synth_capture(rate, n, lam, seed)
+    if iq is None:
+        iq, _ = synth.synth_capture(rate, n, lam, seed)
+    n = len(iq)
     pipe = _capi.StreamPipe(rate, thr, pmf, use_dcblock=dcblock, depth=depth, lib=lib, device=(-1 if device is None else device.index or 0))
     front = pipe.front()
     lo = max(min_chunk or 0, front + 1)

@@ -38,6 +38,35 @@ struct DevBuf {
 
 char g_create_err[256] = "";
 
+// What run_refine was last asked for (a speculative scan that met more candidates than its capacity is redone from this)
+struct RefineArgs {
+    const float *bb = nullptr, *avg = nullptr;
+    uint32_t nseg = 0, stride = 0;
+    int mode = 0;
+    uint32_t end_j = 0xFFFFFFFFu;
+};
+
+// What the tail of a scan (chain_finish: walk, marking, extraction, slicing, completion ticket) is asked for, beyond the
+// records that are resident.  Built by the caller, passed by value; a deferred tail keeps its copy in am_ctx::Pending.
+struct TailReq {
+    uint32_t cur0 = 0;                 // where the greedy scan starts (array coordinate; with an entry source: composed on the device)
+    uint32_t emit_max = 0xFFFFFFFFu;   // last refined position that may emit
+    uint64_t base_abs = 0;             // absolute index of array coordinate 0
+    uint32_t max_hits = 0;             // bound on the hits (they lie at least 240 chips apart)
+    uint32_t own_lo = 0, own_hi = 0xFFFFFFFFu;   // first-stage positions this scan owns
+    long long e_off = 0;
+    bool keep_bursts = false;          // block-level scan: bursts + tags go to h_bursts / h_tags, no packets are handed out
+    bool keep_tags = false;            // AM_F_KEEP_TAGS: the packets' bursts + tags as well
+    bool defer = false;                // enqueue only: AM_DEFERRED, completion is left to chain_collect
+    bool gate = false;                 // the address gate runs behind the slicing (scans that hand out packets, gate_mode != 0)
+    bool copy_tail = false;            // time shards: am_shard_keep_tail's copy goes between the slicing and the ticket
+    bool has_entry = false;            // time shards: the start position is composed on the device from `entry`
+    am_entry_src entry;
+    const uint32_t *flag_src = nullptr;   // this device word comes to the host with the completion ticket (pin_scalars[4])
+    const uint64_t *word_src = nullptr;   // ... and this 64-bit one (pin_scalars[12..13]: where the scan left the chunk)
+    hipEvent_t walk_event = nullptr;      // recorded behind the block walk (am_spipe: what the next chunk's resolve step waits for)
+};
+
 } // namespace
 
 struct am_ctx {
@@ -77,9 +106,7 @@ struct am_ctx {
     const uint32_t *Mdev = nullptr;
     double spec_density = 0.0;    // candidates per position, previous scan
     double spec_floor = 16384.0;  // slack added to the extrapolated capacity (AIRMODES_SPEC_FLOOR, tests)
-    uint32_t ref_nseg = 0, ref_stride = 0, ref_endj = 0;   // arguments of the last run_refine (for the redo)
-    int ref_mode = 0;
-    const float *ref_bb = nullptr, *ref_avg = nullptr;
+    RefineArgs ref;               // arguments of the last run_refine (for the redo)
     int use_dcblock = 0;          // a2: dc_blocker_cc(100*spc, False) in front of |.|^2 (rx_path.py:39-41)
     const float *zt_base[2] = {nullptr, nullptr};   // where the zero tail of bb / avg was last written
     uint64_t zt_n[2] = {0, 0};
@@ -98,23 +125,19 @@ struct am_ctx {
     bool force_generic = false;   // (test builds: AIRMODES_GENERIC=1) use the rate-generic kernels only
     // am_submit_iq / am_collect: the scan of an independent batch is enqueued by one call and completed by the other,
     // so that one host thread can keep several contexts busy (am_pipe below)
-    bool defer = false;           // set while am_submit_iq runs: chain_finish enqueues and returns AM_DEFERRED
     struct Pending {
         bool active = false;      // a submitted batch awaits am_collect
         bool scanned = false;     // ... and it has a scan in flight (a ticket to wait for)
-        uint32_t seq = 0, M = 0, n_max = 0, cur0 = 0, emax = 0, max_hits = 0, j0 = 0, j1 = 0;
+        uint32_t seq = 0, M = 0, n_max = 0, j0 = 0, j1 = 0;
         const uint32_t *Mp = nullptr;
-        uint64_t out_abs0 = 0, P1 = 0;
+        TailReq req;              // what its tail was asked for (chain_collect; am_collect's redo)
         double T0 = 0.0;
     } pend;
-    bool keep_tags = false;       // AM_F_KEEP_TAGS of the call in progress: bursts + tags of its hits stay for am_fetch_tags
     uint64_t rec_base = 0;        // absolute index of array coordinate 0 of the resident records (am_fetch_candidates)
     bool poison = false;          // (test builds: AIRMODES_POISON=1) NaN-fill the sparse bb / reference-level arrays before every scan
-    bool rows_in_gather = true;      // 64 Msps: bb rows around candidates from IQ in am_k_gather_wg (test builds: AIRMODES_ROWS_FE=1 keeps the front end's)
-    bool rows_from_iq = false;       // ... in force for the scan in flight
-    bool rows_max = true;            // ... with a maximum per row for am_k_refine_late (test builds: AIRMODES_ROWS_MAX=0 keeps round 5's first form)
+    bool rows_from_iq = false;       // 64 Msps: the bb rows around candidates are formed from IQ behind the front end, not written by it (the scan in flight)
     bool fused_refine = true;        // 64 Msps (round 6): list + rows + refinement in one launch, the rows in LDS (am_k_refine_seg); test builds:
-                                     // AIRMODES_FUSED_REFINE=0 keeps am_k_gather_wg<1> + am_k_refine_late
+                                     // AIRMODES_FUSED_REFINE=0 keeps am_k_gather_wg<1> + am_k_refine_late with a maximum per row
     DevBuf bbmax;
     am_rows_args rows = {};
     bool allow_stream = true;        // (test builds: AIRMODES_FE=2) keeps the tile kernel (am_k_fe2, dense bb) where the streaming one would run
@@ -181,12 +204,7 @@ struct am_ctx {
     void *keep_dst = nullptr;           // am_shard_keep_tail: copied between a resolve step's slicing and its completion
     const void *keep_src = nullptr;
     uint64_t keep_bytes = 0;
-    bool resolving_shard = false;       // set around chain_finish by the am_shard_resolve* calls
     DevBuf shard_exit;                  // device word: where the scan left this context's chunk in the last resolved step (0: none)
-    const am_entry_src *entry_src = nullptr; // set around chain_finish: the scan's start position is composed on the device (time shards)
-    const uint32_t *flag_src = nullptr; // ... and this device word is handed to the host with the completion ticket (pin_scalars[4])
-    hipEvent_t walk_event = nullptr;    // ... recorded behind the block walk (am_spipe: the next chunk's resolve step waits for this, not for the slicing)
-    const uint64_t *word_src = nullptr; // ... and this 64-bit one (pin_scalars[12..13]: where the scan left the chunk -- am_spipe's books)
 
     // pinned host memory the tail kernels write into directly
     am_packet *pin_packets = nullptr;
@@ -281,6 +299,16 @@ int ensure_shard_exit(am_ctx *c)
     int rc = ensure(c, c->shard_exit, 2 * sizeof(uint64_t));
     if (rc != AM_OK) return rc;
     if (hipMemsetAsync(c->shard_exit.p, 0, 2 * sizeof(uint64_t), c->stream) != hipSuccess) return fail(c, AM_EHIP, "hipMemsetAsync");
+    return AM_OK;
+}
+
+// the pinned scalar block the tail kernels write into: [0..2] results of the slice launch, [3..4] time shards, [5] chained-scan
+// error, [8] completion ticket, [9..11] address gate, [12..13] a time chunk's exit word
+int ensure_pin_scalars(am_ctx *c)
+{
+    if (c->pin_scalars) return AM_OK;
+    HIPCHK(c, hipHostMalloc((void **)&c->pin_scalars, 16 * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
+    memset(c->pin_scalars, 0, 16 * sizeof(uint32_t));
     return AM_OK;
 }
 
@@ -469,9 +497,9 @@ static int scan_path(const am_ctx *c, bool dense_wanted)
 // Scan of the per-segment candidate counts and read-back of the total; then either the
 // refinement kernel (generic path: candidates only) or the gather of the records the fused
 // kernel already produced.  Leaves the flat records (pos, e, tgt, inavg, valid) on the device.
-int run_refine(am_ctx *c, const float *bb, const float *avg, uint32_t nseg, uint32_t seg_stride, int mode,
-               uint32_t *M_out, uint32_t end_j = 0xFFFFFFFFu, uint32_t spec_cap = 0)
+int run_refine(am_ctx *c, const RefineArgs a, uint32_t *M_out, uint32_t spec_cap = 0)
 {
+    const auto [bb, avg, nseg, seg_stride, mode, end_j] = a;
     *M_out = 0;
     c->spec_now = false;
     c->Mdev = nullptr;
@@ -490,8 +518,7 @@ int run_refine(am_ctx *c, const float *bb, const float *avg, uint32_t nseg, uint
         }
     } else
         HIPCHK(c, am_launch_scan_u32((uint32_t *)c->blk_cnt.p, (uint32_t *)c->blk_off.p, nseg, c->stream));
-    c->ref_bb = bb; c->ref_avg = avg; c->ref_nseg = nseg; c->ref_stride = seg_stride; c->ref_mode = mode;
-    c->ref_endj = end_j;
+    c->ref = a;
     uint32_t M = 0;
     const uint32_t *Mp = nullptr;
     if (spec_cap && mode >= 2) {
@@ -573,6 +600,15 @@ int run_refine(am_ctx *c, const float *bb, const float *avg, uint32_t nseg, uint
     return AM_OK;
 }
 
+// Capacity a speculative scan over npos positions is launched for, extrapolated from the previous scan's candidate density;
+// 0: no estimate (or AIRMODES_NO_SPEC), the scan reads its exact count back (a capacity of 0 would mean "exact": at least one slot)
+uint32_t spec_capacity(const am_ctx *c, uint32_t npos)
+{
+    if (!c->allow_spec || !(c->spec_density > 0.0)) return 0;
+    const double want = c->spec_density * (double)npos * 1.25 + c->spec_floor;
+    return (uint32_t)std::max<double>(1.0, std::min<double>(want, std::min<double>((double)npos, 4.0e9)));
+}
+
 // Candidate detection + refinement over positions [j0, j1) of existing device arrays bb/avg
 // (block-level entry point: the generic detection kernel).
 int run_candidates(am_ctx *c, const float *bb, const float *avg, uint32_t j0, uint32_t j1, uint32_t *M_out)
@@ -586,7 +622,7 @@ int run_candidates(am_ctx *c, const float *bb, const float *avg, uint32_t j0, ui
     ENSURE(c, c->blk_off, ((size_t)nblk + 1) * sizeof(uint32_t));
     HIPCHK(c, am_launch_detect(bb, avg, j0, j1, c->geom, c->thr_lin, (uint32_t *)c->cand_seg.p,
                                (uint32_t *)c->blk_cnt.p, nblk, c->stream));
-    return run_refine(c, bb, avg, nblk, AM_DET_PER_BLOCK, 0, M_out);
+    return run_refine(c, {bb, avg, nblk, AM_DET_PER_BLOCK, 0}, M_out);
 }
 
 // IQ -> bb, avg and the refined candidate records for positions [j0, j1): the fused
@@ -628,12 +664,12 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
         }
         // 64 Msps (a bitmap word = one 32-sample chip, lag 288): the bb rows around candidates are formed from the samples by
         // am_k_gather_wg, not written by the front end (~42 MB of stores per 64 M samples that the dominant kernel does not make)
-        c->rows_from_iq = c->rows_in_gather && am_fe4_unit(c->spc) == 32 && am_fe4_lag(c->spc) == 288;
+        c->rows_from_iq = am_fe4_unit(c->spc) == 32 && am_fe4_lag(c->spc) == 288;
         c->rows.iq = c->rows_from_iq ? src : nullptr;
         c->rows.src_abs0 = (long long)src_abs0; c->rows.src_abs1 = (long long)src_abs1; c->rows.out_abs0 = (long long)out_abs0;
         c->rows.out_n = (long long)out_n; c->rows.bb_sparse = bb; c->rows.use_pmf = c->use_pmf;
         c->rows.bb_max = nullptr;
-        if (c->rows_from_iq && c->rows_max && !c->fused_refine) {
+        if (c->rows_from_iq && !c->fused_refine) {
             // one float per array chip: the largest bb of every row formed (am_k_refine_late: whole chips of a quiet zone)
             ENSURE(c, c->bbmax, ((size_t)(out_n / 32) + 64) * sizeof(float));
             c->rows.bb_max = (float *)c->bbmax.p;
@@ -666,14 +702,8 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
         c->bb_sparse = true;
         c->last_fe = 3;
         const uint64_t endj3 = src_abs1 > out_abs0 ? src_abs1 - out_abs0 : 0;
-        uint32_t cap3 = 0;
-        if (may_speculate && c->allow_spec && c->spec_density > 0.0) {
-            const double npos = (double)(j1 - j0);
-            const double want = c->spec_density * npos * 1.25 + c->spec_floor;
-            cap3 = (uint32_t)std::max<double>(1.0, std::min<double>(want, std::min<double>(npos, 4.0e9)));
-        }
-        return run_refine(c, bb, (const float *)c->avg.p, c->fe_nwg, 0, 3, M_out,
-                          (uint32_t)std::min<uint64_t>(endj3, 0xFFFFFFFFull), cap3);
+        return run_refine(c, {bb, (const float *)c->avg.p, c->fe_nwg, 0, 3, (uint32_t)std::min<uint64_t>(endj3, 0xFFFFFFFFull)}, M_out,
+                          may_speculate ? spec_capacity(c, j1 - j0) : 0u);
     }
 #if AM_WITH_TILE_KERNEL
     const unsigned T2 = am_fe2_tile(c->spc);
@@ -697,15 +727,8 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     c->dom_timed = true;
     const uint64_t endj = src_abs1 > out_abs0 ? src_abs1 - out_abs0 : 0;
-    uint32_t spec_cap = 0;
-    if (may_speculate && c->allow_spec && avg_sparse && c->spec_density > 0.0) {
-        // (a capacity of 0 would mean "exact": at least one slot)
-        const double npos = (double)(j1 - j0);
-        const double want = c->spec_density * npos * 1.25 + c->spec_floor;
-        spec_cap = (uint32_t)std::max<double>(1.0, std::min<double>(want, std::min<double>(npos, 4.0e9)));
-    }
-    return run_refine(c, bb, avg_sparse ? avg_sparse : avg, nt, tl, 2, M_out,
-                      (uint32_t)std::min<uint64_t>(endj, 0xFFFFFFFFull), spec_cap);
+    return run_refine(c, {bb, avg_sparse ? avg_sparse : avg, nt, tl, 2, (uint32_t)std::min<uint64_t>(endj, 0xFFFFFFFFull)}, M_out,
+                      may_speculate && avg_sparse ? spec_capacity(c, j1 - j0) : 0u);
 #else
     return fail(c, AM_EINVAL, "internal: no kernel for this scan");
 #endif
@@ -798,7 +821,7 @@ int chain_prepare(am_ctx *c, uint32_t M, bool want_last, const uint32_t *Mp = nu
 }
 
 // The part of chain_finish behind the completion ticket: counts, resume position, accepted packets.
-int chain_collect(am_ctx *c, uint32_t M, const uint32_t *Mp, uint32_t n_max, bool keep_bursts, uint32_t *final_cur)
+int chain_collect(am_ctx *c, const TailReq &req, uint32_t M, const uint32_t *Mp, uint32_t n_max, uint32_t *final_cur)
 {
     c->tail_synced = true;
     if (c->pin_scalars[5]) {
@@ -817,7 +840,7 @@ int chain_collect(am_ctx *c, uint32_t M, const uint32_t *Mp, uint32_t n_max, boo
     c->n_hits = n_emit;
     if (c->gate_live)                                        // (an accepted scan: a repeated one returned above)
         for (int k = 0; k < 3; k++) c->gate_stat[k] += c->pin_scalars[9 + k];
-    if (!keep_bursts) {
+    if (!req.keep_bursts) {
         const double TC = am_now_us();
         for (uint32_t i = 0; i < n_emit; i++) {
             if (!c->pin_packets[i].reserved[0]) continue;      // rejected: only this flag was written
@@ -825,7 +848,7 @@ int chain_collect(am_ctx *c, uint32_t M, const uint32_t *Mp, uint32_t n_max, boo
             c->pending.back().reserved[0] = 0;
         }
         c->ht[7] += am_now_us() - TC;
-        if (!c->keep_tags) return AM_OK;
+        if (!req.keep_tags) return AM_OK;
     }
     c->h_tags.assign(c->pin_tags, c->pin_tags + n_emit);
     if (n_emit) {
@@ -837,14 +860,16 @@ int chain_collect(am_ctx *c, uint32_t M, const uint32_t *Mp, uint32_t n_max, boo
     return AM_OK;
 }
 
-// Greedy chain, part 2: mark the candidates the scan visits when it starts at cur0, then extract
-// and slice the hits (e <= emit_max, first-stage position in [own_lo, own_hi)).
+// Greedy chain, part 2: mark the candidates the scan visits when it starts at req.cur0, then extract
+// and slice the hits (e <= emit_max, first-stage position in [own_lo, own_hi)).  Everything the caller decides is in
+// `req`; the rest is the resident scan (chain_prepare's records, the samples they were formed from).
 // keep_bursts (block-level scan): fills h_tags + h_bursts.  Otherwise (streaming / sharded scan) the tags
 // stay on the device and the accepted packets go straight from pinned memory to `pending`.
-int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, uint64_t base_abs,
-                 bool keep_bursts, uint32_t *final_cur, uint32_t max_hits, uint32_t own_lo = 0,
-                 uint32_t own_hi = 0xFFFFFFFFu, long long e_off = 0)
+int chain_finish(am_ctx *c, const float *bb, const TailReq &req, uint32_t *final_cur)
 {
+    const uint32_t cur0 = req.cur0, emit_max = req.emit_max;
+    const uint64_t base_abs = req.base_abs;
+    const bool keep_bursts = req.keep_bursts, gate = req.gate;
     const uint32_t M = c->chain_M;
     const uint32_t *Mp = c->chain_Mp;
     c->h_packets.clear();
@@ -861,18 +886,18 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
     // Hits are at least 240*spc apart, so their number is bounded by the span of the candidates;
     // everything downstream is launched for that bound and reads the real count on the device.
     // Packets and tags land directly in pinned host memory: one synchronisation for the whole tail.
-    const uint32_t n_max = max_hits < M ? max_hits : M;
+    const uint32_t n_max = req.max_hits < M ? req.max_hits : M;
     uint32_t *n_ptr = (uint32_t *)c->cblk_off.p + nb;
     ENSURE(c, c->emit_idx, (size_t)n_max * sizeof(uint4));     // one record per hit: {candidate, position, refined position, reference level}
     if (int rc = ensure_slots(c, c->lb_mark, nb); rc != AM_OK) return rc;
     // which candidates the scan visits, which of them are hits, and their ordered list -- one launch after the walk
     HIPCHK(c, am_launch_chain_visit((uint32_t *)c->pos.p, (uint32_t *)c->jump.p, M, cur0, (uint32_t *)c->cscratch.p,
-                                    (uint8_t *)c->valid.p, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p, emit_max, own_lo,
-                                    own_hi, (uint4 *)c->emit_idx.p, n_ptr, (unsigned long long *)c->lb_mark.p,
+                                    (uint8_t *)c->valid.p, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p, emit_max, req.own_lo,
+                                    req.own_hi, (uint4 *)c->emit_idx.p, n_ptr, (unsigned long long *)c->lb_mark.p,
                                     next_epoch(c), (uint32_t *)c->scalars.p + 11, &c->tk_base[1],
                                     (uint32_t *)c->scalars.p, emit_max == 0xFFFFFFFFu ? 1 : 0, c->stream, Mp,
-                                    c->entry_src, (const float *)c->inavg.p, c->walk_event));
-    const bool keep_dev = keep_bursts || c->keep_tags;       // the bursts and their tags leave the kernel
+                                    req.has_entry ? &req.entry : nullptr, (const float *)c->inavg.p, req.walk_event));
+    const bool keep_dev = keep_bursts || req.keep_tags;      // the bursts and their tags leave the kernel
     if (keep_dev) ENSURE(c, c->bursts, (size_t)n_max * AM_BURST * sizeof(float));
     if (c->pin_cap < n_max) {
         if (c->pin_packets) (void)hipHostFree(c->pin_packets);
@@ -883,12 +908,7 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
         HIPCHK(c, hipHostMalloc((void **)&c->pin_tags, want * sizeof(am_tag), hipHostMallocCoherent | hipHostMallocMapped));
         c->pin_cap = (uint32_t)want;
     }
-    if (!c->pin_scalars) {
-        HIPCHK(c, hipHostMalloc((void **)&c->pin_scalars, 16 * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
-        memset(c->pin_scalars, 0, 16 * sizeof(uint32_t));     // [0..2] results of the slice launch, [3..4] time shards, [5] chained-scan error, [8] completion ticket, [9..11] address gate
-    }
-    // the address gate covers the scans that hand out packets (not the block-level preamble, not the time shards, which refuse it)
-    const bool gate = c->gate_mode != 0 && !keep_bursts && !c->resolving_shard && !c->flag_src && !c->word_src;
+    if (int rc = ensure_pin_scalars(c); rc != AM_OK) return rc;
     if (gate)
         if (int rc = gate_prepare(c, n_max, n_ptr, c->pin_packets); rc != AM_OK) return rc;
     // extraction + slicing in one launch; the bursts and their tags leave the kernel only for the block-level
@@ -913,13 +933,13 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
     else
     HIPCHK(c, am_launch_extract_slice(bb, (const float *)c->inavg.p, c->spc, c->frac ? (const int *)c->chip_idx.p : nullptr,
                                       c->geom.hist0, (const uint4 *)c->emit_idx.p, n_ptr, n_max,
-                                      (uint32_t *)c->pos.p, (uint32_t *)c->e.p, base_abs, e_off, c->rate_i,
+                                      (uint32_t *)c->pos.p, (uint32_t *)c->e.p, base_abs, req.e_off, c->rate_i,
                                       (const am_time_tag *)c->tt_dev.p, (uint32_t)c->tt.size(),
                                       keep_dev ? (float *)c->bursts.p : nullptr,
                                       keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p, c->pin_packets,
                                       (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp, c->fix_bits, gate ? 1 : 0));
     if (gate) HIPCHK(c, am_launch_gate(c->ga, n_max, c->stream));     // behind the slicing launch, in front of the ticket
-    if (c->keep_bytes && c->resolving_shard)
+    if (req.copy_tail)
         // time shards: the samples the next step needs in front of its chunk, kept while this step's are still in place
         // (am_shard_keep_tail; behind the extraction kernel, which still reads them; complete when the ticket is seen)
         HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
@@ -927,35 +947,27 @@ int chain_finish(am_ctx *c, const float *bb, uint32_t cur0, uint32_t emit_max, u
     if (gate)
         HIPCHK(c, am_launch_gate_ticket(c->pin_scalars + 8, seq, c->ga.cnt, c->pin_scalars + 9, c->stream));
     else
-    HIPCHK(c, am_launch_ticket(c->pin_scalars + 8, seq, c->stream, c->flag_src, c->flag_src ? c->pin_scalars + 4 : nullptr,
-                               c->word_src, c->word_src ? reinterpret_cast<uint64_t *>(c->pin_scalars + 12) : nullptr));
+    HIPCHK(c, am_launch_ticket(c->pin_scalars + 8, seq, c->stream, req.flag_src, req.flag_src ? c->pin_scalars + 4 : nullptr,
+                               req.word_src, req.word_src ? reinterpret_cast<uint64_t *>(c->pin_scalars + 12) : nullptr));
     c->gate_live = gate;
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));          // end of the device work of this scan (behind the ticket)
     c->total_pending = true;
-    if (c->defer && !keep_bursts) {
+    if (req.defer && !keep_bursts) {
         c->pend.scanned = true;
         c->pend.seq = seq; c->pend.M = M; c->pend.Mp = Mp; c->pend.n_max = n_max;
+        c->pend.req = req;
         return AM_DEFERRED;
     }
     const double TS = am_now_us();
     HIPCHK(c, wait_for_ticket(c, seq));
     c->ht[5] += am_now_us() - TS;
-    return chain_collect(c, M, Mp, n_max, keep_bursts, final_cur);
+    return chain_collect(c, req, M, Mp, n_max, final_cur);
 }
 
-int run_chain_and_slice(am_ctx *c, const float *bb, const float *, uint32_t M, uint32_t cur0, uint32_t emit_max,
-                        uint64_t base_abs, bool keep_bursts, uint32_t *final_cur, uint32_t max_hits)
+int run_chain_and_slice(am_ctx *c, const float *bb, uint32_t M, const TailReq &req, uint32_t *final_cur)
 {
-    c->h_packets.clear();
-    c->h_tags.clear();
-    c->h_bursts.clear();
-    c->n_hits = 0;
-    c->last_M = M;
-    c->gate_live = false;
-    *final_cur = cur0;
     int rc = chain_prepare(c, M, false, c->spec_now ? c->Mdev : nullptr);
-    if (rc != AM_OK || M == 0) return rc;
-    return chain_finish(c, bb, cur0, emit_max, base_abs, keep_bursts, final_cur, max_hits);
+    return rc != AM_OK ? rc : chain_finish(c, bb, req, final_cur);    // (no candidate: chain_finish leaves empty results)
 }
 
 void collect_accepted(am_ctx *c)
@@ -1023,6 +1035,68 @@ bool flush_limits(const am_ctx *c, uint64_t N, uint64_t *emit_max)
     return true;
 }
 
+// Positions that can be decided now, [P0, return value), when S1 samples (am_process_iq) or items (am_preamble_stream) of the stream
+// exist: all that the end-of-stream rule lets emit if the stream ends here (*emit_max_abs: the last of them, else ~0), otherwise
+// those with a burst and the late shifts of look-ahead -- a hit decided now must also be a hit if the stream ended right here.
+uint64_t decidable(const am_ctx *c, uint64_t P0, uint64_t S1, bool flush, uint64_t *emit_max_abs)
+{
+    *emit_max_abs = ~(uint64_t)0;
+    if (flush) {
+        uint64_t em;
+        if (!flush_limits(c, S1, &em)) return P0;
+        *emit_max_abs = em;
+        return std::max(P0, em + 1);
+    }
+    const uint64_t hold = (uint64_t)(AM_BURST + 4) * (uint64_t)c->spc_hi;
+    return S1 > hold ? std::max(P0, S1 - hold) : P0;
+}
+
+// Books of a scan whose results the host has: candidates per position, what the next scan's capacity is extrapolated from ...
+void note_density(am_ctx *c, uint64_t npos) { c->spec_density = npos ? (double)c->last_M / (double)npos : 0.0; }
+
+// ... and the time of its dominant kernel (both events lie in front of the completion ticket the host has seen)
+void read_dom_ms(am_ctx *c)
+{
+    c->last_dom_ms = 0.0f;
+    if (c->dom_timed && hipEventElapsedTime(&c->last_dom_ms, c->ev[3], c->ev[1]) != hipSuccess) c->ht[6] += 1.0;
+}
+
+// the hits of a block-level scan (h_tags, h_bursts) into the caller's arrays
+int hand_out_tags(am_ctx *c, float *bursts, am_tag *tags, uint64_t cap, uint64_t *n_out)
+{
+    const uint64_t nt = c->h_tags.size();
+    if (n_out) *n_out = nt;
+    if (nt > cap) return fail(c, AM_ECAPACITY, "burst/tag arrays too small");
+    if (nt) {
+        if (!bursts || !tags) return fail(c, AM_EINVAL, "null output");
+        memcpy(bursts, c->h_bursts.data(), nt * AM_BURST * sizeof(float));
+        memcpy(tags, c->h_tags.data(), nt * sizeof(am_tag));
+    }
+    return AM_OK;
+}
+
+// The resolve step of the resident time chunk: false if it has nothing to slice (no candidate, or the end-of-stream rule leaves
+// it no position that may emit); otherwise req is what its tail is asked for.  msgs (device): `world` exit tables of msg_cap
+// entries from which the walk composes the start position itself (scalars and shard_exit exist); null: the caller sets req.cur0.
+bool resolve_plan(const am_ctx *c, const am_shard_exit *msgs, uint32_t world, uint32_t rank, uint32_t msg_cap, TailReq &req)
+{
+    uint64_t em = 0;
+    if (c->chain_M == 0 || (!c->shard_more && (!flush_limits(c, c->shard_total, &em) || em < c->shard_base))) return false;
+    req = TailReq();
+    req.emit_max = c->shard_more ? 0xFFFFFFFEu : (uint32_t)std::min<uint64_t>(em - c->shard_base, 0xFFFFFFFEu);
+    req.base_abs = c->shard_base;
+    req.max_hits = (uint32_t)((c->shard_end - c->shard_start + (uint64_t)c->spc) / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
+    req.copy_tail = c->keep_bytes != 0;
+    if (msgs) {
+        uint32_t *flag_dev = (uint32_t *)c->scalars.p + 5;
+        req.has_entry = true;
+        req.entry.msgs = msgs; req.entry.world = world; req.entry.rank = rank; req.entry.cap = msg_cap;
+        req.entry.base_abs = c->shard_base; req.entry.flags = flag_dev; req.entry.exit_out = (uint64_t *)c->shard_exit.p;
+        req.flag_src = flag_dev;
+    }
+    return true;
+}
+
 } // namespace
 
 extern "C" {
@@ -1083,10 +1157,6 @@ am_ctx *am_create(int device, double rate, float threshold_db, int use_pmf, int 
             c->force_generic = g && g[0] == '1';
             const char *fe = getenv("AIRMODES_FE");
             c->allow_stream = !(fe && fe[0] == '2');
-            const char *rf = getenv("AIRMODES_ROWS_FE");
-            c->rows_in_gather = !(rf && rf[0] == '1');
-            const char *rm = getenv("AIRMODES_ROWS_MAX");
-            c->rows_max = !(rm && rm[0] == '0');
             const char *fr = getenv("AIRMODES_FUSED_REFINE");
             c->fused_refine = fr ? fr[0] == '1' : c->fused_refine;
             const char *po = getenv("AIRMODES_POISON");
@@ -1340,7 +1410,6 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
     c->last_tags = 0;
     const bool flush = (flags & AM_F_FLUSH) != 0;
     const bool dev_in = (flags & AM_F_DEVICE_IN) != 0;
-    c->keep_tags = (flags & AM_F_KEEP_TAGS) != 0;
     c->h_tags.clear();
     c->h_bursts.clear();
     const uint64_t S = (uint64_t)c->spc;
@@ -1373,19 +1442,8 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
 
     // 2. positions that can be decided now
     const uint64_t P0 = c->next_pos;
-    uint64_t P1 = P0;
-    uint64_t emit_max_abs = ~(uint64_t)0;
-    if (flush) {
-        uint64_t em;
-        if (flush_limits(c, S1, &em)) {
-            emit_max_abs = em;
-            if (em + 1 > P0) P1 = em + 1;
-        }
-    } else {
-        // a hit decided now must also be a hit if the stream ended right here
-        const uint64_t hold = (uint64_t)(AM_BURST + 4) * (uint64_t)c->spc_hi;
-        if (S1 > hold && S1 - hold > P0) P1 = S1 - hold;
-    }
+    uint64_t emit_max_abs;
+    const uint64_t P1 = decidable(c, P0, S1, flush, &emit_max_abs);
     if (P1 > P0) {
         const uint64_t out_abs0 = (P0 / L) * L;
         const uint64_t out_n = S1 - out_abs0;
@@ -1414,18 +1472,20 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         if (rc != AM_OK) return rc;
         const double T2 = am_now_us();
         c->ht[0] += T1 - T0; c->ht[1] += T2 - T1;
-        const uint32_t cur0 = c->chain_cur > out_abs0 ? (uint32_t)std::min<uint64_t>(c->chain_cur - out_abs0, 0xFFFFFFF0u) : 0u;
-        const uint32_t emax = emit_max_abs == ~(uint64_t)0 ? 0xFFFFFFFFu : (uint32_t)(emit_max_abs - out_abs0);
-        uint32_t fin = cur0;
-        const uint32_t max_hits = (uint32_t)((P1 - P0 + S) / ((uint64_t)AM_BURST * S) + 2);
-        c->defer = submit;
-        rc = run_chain_and_slice(c, bb, avg, M, cur0, emax, out_abs0, false, &fin, max_hits);
-        c->defer = false;
+        TailReq req;
+        req.cur0 = c->chain_cur > out_abs0 ? (uint32_t)std::min<uint64_t>(c->chain_cur - out_abs0, 0xFFFFFFF0u) : 0u;
+        req.emit_max = emit_max_abs == ~(uint64_t)0 ? 0xFFFFFFFFu : (uint32_t)(emit_max_abs - out_abs0);
+        req.base_abs = out_abs0;
+        req.max_hits = (uint32_t)((P1 - P0 + S) / ((uint64_t)AM_BURST * S) + 2);
+        req.keep_tags = (flags & AM_F_KEEP_TAGS) != 0;
+        req.defer = submit;
+        req.gate = c->gate_mode != 0;                       // these are the scans that hand out packets
+        uint32_t fin = req.cur0;
+        rc = run_chain_and_slice(c, bb, M, req, &fin);
         c->ht[2] += am_now_us() - T2;
         if (rc == AM_DEFERRED) {
-            c->pend.active = true;
-            c->pend.cur0 = cur0; c->pend.emax = emax; c->pend.max_hits = max_hits; c->pend.j0 = j0; c->pend.j1 = j1;
-            c->pend.out_abs0 = out_abs0; c->pend.P1 = P1; c->pend.T0 = T0;
+            c->pend.active = true;                          // (chain_finish filled in scanned / seq / M / Mp / n_max / req)
+            c->pend.j0 = j0; c->pend.j1 = j1; c->pend.T0 = T0;
             return AM_OK;
         }
         if (rc == AM_RETRY_EXACT) {
@@ -1434,17 +1494,16 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
 #endif
             // more candidates than the capacity this scan was launched for: redo the refinement and
             // the chain with the exact count (the fused kernel's outputs are still in place)
-            rc = run_refine(c, c->ref_bb, c->ref_avg, c->ref_nseg, c->ref_stride, c->ref_mode, &M, c->ref_endj, 0);
+            rc = run_refine(c, c->ref, &M);
             if (rc != AM_OK) return rc;
-            fin = cur0;
-            rc = run_chain_and_slice(c, bb, avg, M, cur0, emax, out_abs0, false, &fin, max_hits);
+            rc = run_chain_and_slice(c, bb, M, req, &fin);
         }
         if (rc != AM_OK) return rc;
         // the scan is the stream's: only now do its teaching replies enter the address gate's map (a scan that was repeated
         // above has left nothing there).  Not at the end of a stream: the map ends with it (reset_stream below).
         if (c->gate_live && !flush)
             if (int grc = gate_commit(c, c->n_hits); grc != AM_OK) return grc;
-        c->spec_density = (j1 > j0) ? (double)c->last_M / (double)(j1 - j0) : 0.0;
+        note_density(c, j1 - j0);
         c->last_tags = c->n_hits;
         if (out_abs0 + fin > c->chain_cur) c->chain_cur = out_abs0 + fin;
         c->next_pos = P1;
@@ -1487,8 +1546,7 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
     // (after a scan ev[2] sits behind the completion ticket and may still be in flight: am_last_timing waits
     // for it when somebody asks for the whole-call time)
     if (!c->total_pending) (void)hipEventElapsedTime(&c->last_total_ms, c->ev[0], c->ev[2]);
-    c->last_dom_ms = 0.0f;
-    if (c->dom_timed && hipEventElapsedTime(&c->last_dom_ms, c->ev[3], c->ev[1]) != hipSuccess) c->ht[6] += 1.0;
+    read_dom_ms(c);
     const int hrc = hand_out(c, out, cap, n_out);
     c->ht[3] += am_now_us() - T5; c->ht[4] += am_now_us() - T0; c->ht_n++;
     return hrc;
@@ -1652,19 +1710,20 @@ int am_collect(am_ctx *c, am_packet *out, uint64_t cap, uint64_t *n_out)
         const double TS = am_now_us();
         HIPCHK(c, wait_for_ticket(c, P.seq));
         c->ht[5] += am_now_us() - TS;
-        uint32_t fin = P.cur0, M = P.M;
-        int rc = chain_collect(c, P.M, P.Mp, P.n_max, false, &fin);
+        uint32_t fin = P.req.cur0, M = P.M;
+        int rc = chain_collect(c, P.req, P.M, P.Mp, P.n_max, &fin);
         if (rc == AM_RETRY_EXACT) {
             // more candidates than the capacity the scan was launched for: redo it with the exact count, now
-            rc = run_refine(c, c->ref_bb, c->ref_avg, c->ref_nseg, c->ref_stride, c->ref_mode, &M, c->ref_endj, 0);
+            rc = run_refine(c, c->ref, &M);
             if (rc == AM_OK) {
-                fin = P.cur0;
-                rc = run_chain_and_slice(c, (const float *)c->bb.p, nullptr, M, P.cur0, P.emax, P.out_abs0, false, &fin,
-                                         P.max_hits);
+                TailReq req = P.req;
+                req.defer = false;
+                req.gate = c->gate_mode != 0;
+                rc = run_chain_and_slice(c, (const float *)c->bb.p, M, req, &fin);
             }
         }
         if (rc != AM_OK) { P.active = false; P.scanned = false; reset_stream(c); c->multi_off.clear(); c->multi_em.clear(); return rc; }
-        c->spec_density = (P.j1 > P.j0) ? (double)c->last_M / (double)(P.j1 - P.j0) : 0.0;
+        note_density(c, P.j1 - P.j0);
         c->last_tags = c->n_hits;
     }
     else
@@ -1674,8 +1733,7 @@ int am_collect(am_ctx *c, am_packet *out, uint64_t cap, uint64_t *n_out)
     P.active = false;
     P.scanned = false;
     reset_stream(c);                                                  // (submitted batches end their stream: AM_F_FLUSH)
-    c->last_dom_ms = 0.0f;
-    if (c->dom_timed && hipEventElapsedTime(&c->last_dom_ms, c->ev[3], c->ev[1]) != hipSuccess) c->ht[6] += 1.0;
+    read_dom_ms(c);
     c->ht[4] += am_now_us() - P.T0; c->ht_n++;
     return hand_out(c, out, cap, n_out);
 }
@@ -1786,19 +1844,14 @@ int am_preamble_work(am_ctx *c, const float *in, const float *inavg, uint64_t n,
         uint32_t M = 0, fin = 0;
         int rc = run_candidates(c, bb, avg, 0, (uint32_t)(em + 1), &M);
         if (rc != AM_OK) return rc;
-        rc = run_chain_and_slice(c, bb, avg, M, 0, (uint32_t)em, 0, true, &fin,
-                                 (uint32_t)(n / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2));
+        TailReq req;
+        req.emit_max = (uint32_t)em;
+        req.max_hits = (uint32_t)(n / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
+        req.keep_bursts = true;
+        rc = run_chain_and_slice(c, bb, M, req, &fin);
         if (rc != AM_OK) return rc;
     }
-    const uint64_t nt = c->h_tags.size();
-    if (n_out) *n_out = nt;
-    if (nt > cap) return fail(c, AM_ECAPACITY, "burst/tag arrays too small");
-    if (nt) {
-        if (!bursts || !tags) return fail(c, AM_EINVAL, "null output");
-        memcpy(bursts, c->h_bursts.data(), nt * AM_BURST * sizeof(float));
-        memcpy(tags, c->h_tags.data(), nt * sizeof(am_tag));
-    }
-    return AM_OK;
+    return hand_out_tags(c, bursts, tags, cap, n_out);
 }
 
 // The preamble block as the streaming gr::block it is in the reference (include/gr_air_modes/preamble.h:36-46,
@@ -1838,28 +1891,21 @@ int am_preamble_stream(am_ctx *c, const float *in, const float *inavg, uint64_t 
         }
         ZERO_TAIL(c, 0, bb, nn, pad);
         ZERO_TAIL(c, 1, avg, nn, pad);
-        // positions that can be decided now (as am_process_iq: a hit decided now must also be one if the stream ended here)
+        // positions that can be decided now (as am_process_iq)
         const uint64_t P0 = c->pb_next;
-        uint64_t P1 = P0, emit_max_abs = ~(uint64_t)0;
-        if (flush) {
-            uint64_t em;
-            if (flush_limits(c, S1, &em)) {
-                emit_max_abs = em;
-                if (em + 1 > P0) P1 = em + 1;
-            }
-        } else {
-            const uint64_t hold = (uint64_t)(AM_BURST + 4) * (uint64_t)c->spc_hi;
-            if (S1 > hold && S1 - hold > P0) P1 = S1 - hold;
-        }
+        uint64_t emit_max_abs;
+        const uint64_t P1 = decidable(c, P0, S1, flush, &emit_max_abs);
         if (P1 > P0) {
             uint32_t M = 0, fin = 0;
             int rc = run_candidates(c, bb, avg, (uint32_t)(P0 - A0), (uint32_t)(P1 - A0), &M);
             if (rc != AM_OK) return rc;
-            const uint32_t cur0 = c->pb_cur > A0 ? (uint32_t)std::min<uint64_t>(c->pb_cur - A0, 0xFFFFFFF0u) : 0u;
-            const uint32_t emax = emit_max_abs == ~(uint64_t)0 ? 0xFFFFFFFFu : (uint32_t)(emit_max_abs - A0);
-            fin = cur0;
-            rc = run_chain_and_slice(c, bb, avg, M, cur0, emax, A0, true, &fin,
-                                     (uint32_t)((P1 - P0) / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2));
+            TailReq req;
+            req.cur0 = c->pb_cur > A0 ? (uint32_t)std::min<uint64_t>(c->pb_cur - A0, 0xFFFFFFF0u) : 0u;
+            req.emit_max = emit_max_abs == ~(uint64_t)0 ? 0xFFFFFFFFu : (uint32_t)(emit_max_abs - A0);
+            req.base_abs = A0;
+            req.max_hits = (uint32_t)((P1 - P0) / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
+            req.keep_bursts = true;
+            rc = run_chain_and_slice(c, bb, M, req, &fin);
             if (rc != AM_OK) return rc;
             if (A0 + fin > c->pb_cur) c->pb_cur = A0 + fin;
             c->pb_next = P1;
@@ -1880,7 +1926,6 @@ int am_preamble_stream(am_ctx *c, const float *in, const float *inavg, uint64_t 
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));          // (the caller may reuse its buffers)
     }
-    const uint64_t nt = c->h_tags.size();
     if (flush) {
         // (the hits were copied to the host vectors above; the stream starts over at item 0)
         std::vector<am_tag> keep_t = c->h_tags;
@@ -1889,14 +1934,7 @@ int am_preamble_stream(am_ctx *c, const float *in, const float *inavg, uint64_t 
         c->h_tags.swap(keep_t);
         c->h_bursts.swap(keep_b);
     }
-    if (n_out) *n_out = nt;
-    if (nt > cap) return fail(c, AM_ECAPACITY, "burst/tag arrays too small");
-    if (nt) {
-        if (!bursts || !tags) return fail(c, AM_EINVAL, "null output");
-        memcpy(bursts, c->h_bursts.data(), nt * AM_BURST * sizeof(float));
-        memcpy(tags, c->h_tags.data(), nt * sizeof(am_tag));
-    }
-    return AM_OK;
+    return hand_out_tags(c, bursts, tags, cap, n_out);
 }
 
 int am_slicer_work(am_ctx *c, const float *bursts, const am_tag *tags, uint64_t nb, uint32_t flags,
@@ -2117,10 +2155,7 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
         if (rc != AM_OK) return rc;
         n_dev = (uint32_t)std::min<uint64_t>(M, lead + 1);
         uint32_t actual = M;
-        if (!c->pin_scalars) {
-            HIPCHK(c, hipHostMalloc((void **)&c->pin_scalars, 16 * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
-            memset(c->pin_scalars, 0, 16 * sizeof(uint32_t));
-        }
+        if (int rcp = ensure_pin_scalars(c); rcp != AM_OK) return rcp;
         if (n_dev) {
             // the table goes straight to pinned host memory; the host then reads it up to its last entry
             if (c->pin_exit_cap < n_dev) {
@@ -2148,12 +2183,11 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
 #if defined(AM_TEST_KNOBS)
         if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: shard capacity %u < %u candidates, scan redone\n", M, actual);
 #endif
-        rc = run_refine(c, c->ref_bb, c->ref_avg, c->ref_nseg, c->ref_stride, c->ref_mode, &M, c->ref_endj, 0);
+        rc = run_refine(c, c->ref, &M);
         if (rc != AM_OK) return rc;
     }
-    c->spec_density = (P1 > P0) ? (double)c->last_M / (double)(P1 - P0) : 0.0;
-    c->last_dom_ms = 0.0f;
-    if (c->dom_timed && hipEventElapsedTime(&c->last_dom_ms, c->ev[3], c->ev[1]) != hipSuccess) c->ht[6] += 1.0;
+    note_density(c, P1 - P0);
+    read_dom_ms(c);
     uint64_t nt = 0;
     // (a capacity launch may have written an end marker {pos = ~0} behind the last real candidate: not an entry)
     const uint32_t n_real = (uint32_t)std::min<uint64_t>(n_dev, c->last_M);
@@ -2275,22 +2309,17 @@ int am_shard_resolve(am_ctx *c, uint64_t cur_in, am_packet *out, uint64_t cap, u
     HIPCHK(c, hipSetDevice(c->device));
     c->pending.clear();
     c->last_tags = 0;
-    uint64_t em = 0;
-    if (c->chain_M == 0 || (!c->shard_more && (!flush_limits(c, c->shard_total, &em) || em < c->shard_base))) {
+    TailReq req;
+    if (!resolve_plan(c, nullptr, 0, 0, 0, req)) {
         if (c->keep_bytes) {                                    // (nothing to slice: the tail is still kept)
             HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         return AM_OK;
     }
-    const uint32_t cur0 = cur_in > c->shard_base ? (uint32_t)std::min<uint64_t>(cur_in - c->shard_base, 0xFFFFFFF0u) : 0u;
-    const uint32_t emax = c->shard_more ? 0xFFFFFFFEu : (uint32_t)std::min<uint64_t>(em - c->shard_base, 0xFFFFFFFEu);
+    req.cur0 = cur_in > c->shard_base ? (uint32_t)std::min<uint64_t>(cur_in - c->shard_base, 0xFFFFFFF0u) : 0u;
     uint32_t fin = 0;
-    const uint32_t max_hits = (uint32_t)((c->shard_end - c->shard_start + (uint64_t)c->spc) /
-                                         ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
-    c->resolving_shard = true;
-    int rc = chain_finish(c, (const float *)c->bb.p, cur0, emax, c->shard_base, false, &fin, max_hits);
-    c->resolving_shard = false;
+    int rc = chain_finish(c, (const float *)c->bb.p, req, &fin);
     if (rc != AM_OK) return rc;
     c->last_tags = c->n_hits;
     return hand_out(c, out, cap, n_out);
@@ -2308,7 +2337,6 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
     HIPCHK(c, hipSetDevice(c->device));
     c->pending.clear();
     c->last_tags = 0;
-    uint64_t em = 0;
     if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
     uint32_t *cur0_dev = (uint32_t *)c->scalars.p + 4, *flag_dev = (uint32_t *)c->scalars.p + 5;
     // the entry position of this chunk is composed from everybody's exit tables on the device: by the block walk itself, or
@@ -2316,7 +2344,8 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
     // so on every rank alike
     // (the flag is written, 0 or 1, by whichever kernel composes the entry: no fill in front of it)
     if (int rce = ensure_shard_exit(c); rce != AM_OK) return rce;
-    if (c->chain_M == 0 || (!c->shard_more && (!flush_limits(c, c->shard_total, &em) || em < c->shard_base))) {
+    TailReq req;                                                // (entry.cur_in stays null: the scan position comes from the last rank's header)
+    if (!resolve_plan(c, msgs_dev, world, rank, (uint32_t)msg_cap, req)) {
         HIPCHK(c, am_launch_shard_entry(msgs_dev, world, rank, (uint32_t)msg_cap, c->shard_base, cur0_dev, flag_dev,
                                         (uint64_t *)c->shard_exit.p, c->stream));
         uint32_t f = 0;
@@ -2326,30 +2355,15 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
         *redo = f ? 1 : 0;
         return AM_OK;
     }
-    const uint32_t emax = c->shard_more ? 0xFFFFFFFEu : (uint32_t)std::min<uint64_t>(em - c->shard_base, 0xFFFFFFFEu);
     uint32_t fin = 0;
-    const uint32_t max_hits = (uint32_t)((c->shard_end - c->shard_start + (uint64_t)c->spc) /
-                                         ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
-    am_entry_src es;
-    es.msgs = msgs_dev; es.world = world; es.rank = rank; es.cap = (uint32_t)msg_cap; es.base_abs = c->shard_base; es.flags = flag_dev;
-    es.exit_out = (uint64_t *)c->shard_exit.p;
-    es.cur_in = nullptr;                                        // (the scan position comes from the last rank's header)
-    c->entry_src = &es;
-    c->flag_src = flag_dev;
-    c->resolving_shard = true;
-    int rc = chain_finish(c, (const float *)c->bb.p, 0, emax, c->shard_base, false, &fin, max_hits);
-    c->resolving_shard = false;
-    c->entry_src = nullptr;
-    c->flag_src = nullptr;
+    int rc = chain_finish(c, (const float *)c->bb.p, req, &fin);
     // the dominant kernel's event pair of this step's scan (am_shard_scan_async only enqueued): both events lie in front of
-    // the completion ticket chain_finish waited for
-    c->last_dom_ms = 0.0f;
-    if ((rc == AM_OK || rc == AM_RETRY_EXACT) && c->dom_timed &&
-        hipEventElapsedTime(&c->last_dom_ms, c->ev[3], c->ev[1]) != hipSuccess) c->ht[6] += 1.0;
+    // the completion ticket chain_finish waited for -- also where the scan outgrew its capacity
+    if (rc != AM_OK && rc != AM_RETRY_EXACT) { c->last_dom_ms = 0.0f; return rc; }
+    read_dom_ms(c);
     if (rc == AM_RETRY_EXACT) { c->pending.clear(); *redo = 1; return AM_OK; }   // more candidates than the capacity the scan was launched for
-    if (rc != AM_OK) return rc;
     if (c->pin_scalars[4]) { c->pending.clear(); *redo = 1; return AM_OK; }       // a table did not fit its message
-    c->spec_density = (c->shard_end > c->shard_start) ? (double)c->last_M / (double)(c->shard_end - c->shard_start) : 0.0;
+    note_density(c, c->shard_end - c->shard_start);
     c->last_tags = c->n_hits;
     return hand_out(c, out, cap, n_out);
 }
@@ -2424,14 +2438,11 @@ static int shard_resolve_enqueue(am_ctx *c, const am_shard_exit *msgs, uint32_t 
     if (int rcs = ensure_scalars(c); rcs != AM_OK) return rcs;
     if (int rce = ensure_shard_exit(c); rce != AM_OK) return rce;
     uint32_t *cur0_dev = (uint32_t *)c->scalars.p + 4, *flag_dev = (uint32_t *)c->scalars.p + 5;
-    if (!c->pin_scalars) {
-        HIPCHK(c, hipHostMalloc((void **)&c->pin_scalars, 16 * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
-        memset(c->pin_scalars, 0, 16 * sizeof(uint32_t));
-    }
+    if (int rcp = ensure_pin_scalars(c); rcp != AM_OK) return rcp;
     am_ctx::Pending &P = c->pend;
     P = am_ctx::Pending();
-    uint64_t em = 0;
-    if (c->chain_M == 0 || (!c->shard_more && (!flush_limits(c, c->shard_total, &em) || em < c->shard_base))) {
+    TailReq req;
+    if (!resolve_plan(c, msgs, world, rank, msg_cap, req)) {
         // nothing to slice: the entry is still composed (the chunk passes the scan position on), one ticket
         HIPCHK(c, am_launch_shard_entry(msgs, world, rank, msg_cap, c->shard_base, cur0_dev, flag_dev, (uint64_t *)c->shard_exit.p, c->stream, cur_in,
                                         carry_out));
@@ -2443,27 +2454,14 @@ static int shard_resolve_enqueue(am_ctx *c, const am_shard_exit *msgs, uint32_t 
         P.active = true; P.scanned = false; P.seq = seq;
         return AM_OK;
     }
-    const uint32_t emax = c->shard_more ? 0xFFFFFFFEu : (uint32_t)std::min<uint64_t>(em - c->shard_base, 0xFFFFFFFEu);
+    req.entry.cur_in = cur_in; req.entry.carry_out = carry_out;
+    req.word_src = (const uint64_t *)c->shard_exit.p;
+    req.walk_event = walk_done;
+    req.defer = true;
     uint32_t fin = 0;
-    const uint32_t max_hits = (uint32_t)((c->shard_end - c->shard_start + (uint64_t)c->spc) / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
-    am_entry_src es;
-    es.msgs = msgs; es.world = world; es.rank = rank; es.cap = msg_cap; es.base_abs = c->shard_base; es.flags = flag_dev;
-    es.exit_out = (uint64_t *)c->shard_exit.p; es.cur_in = cur_in; es.carry_out = carry_out;
-    c->entry_src = &es;
-    c->flag_src = flag_dev;
-    c->word_src = (const uint64_t *)c->shard_exit.p;
-    c->walk_event = walk_done;
-    c->resolving_shard = true;
-    c->defer = true;
-    int rc = chain_finish(c, (const float *)c->bb.p, 0, emax, c->shard_base, false, &fin, max_hits);
-    c->defer = false;
-    c->resolving_shard = false;
-    c->entry_src = nullptr;
-    c->flag_src = nullptr;
-    c->word_src = nullptr;
-    c->walk_event = nullptr;
+    int rc = chain_finish(c, (const float *)c->bb.p, req, &fin);
     if (rc != AM_DEFERRED) return rc == AM_OK ? fail(c, AM_EHIP, "internal: the resolve step was not deferred") : rc;
-    P.active = true;                                            // (chain_finish filled in scanned / seq / M / Mp / n_max)
+    P.active = true;                                            // (chain_finish filled in scanned / seq / M / Mp / n_max / req)
     return AM_OK;
 }
 
@@ -2479,7 +2477,7 @@ static int shard_resolve_complete(am_ctx *c, int *redo, uint64_t *exit_after)
     int rc = AM_OK;
     if (P.scanned) {
         uint32_t fin = 0;
-        rc = chain_collect(c, P.M, P.Mp, P.n_max, false, &fin);
+        rc = chain_collect(c, P.req, P.M, P.Mp, P.n_max, &fin);
         if (rc == AM_RETRY_EXACT) { *redo = 1; rc = AM_OK; }
     } else
         c->tail_synced = true;
@@ -2488,10 +2486,9 @@ static int shard_resolve_complete(am_ctx *c, int *redo, uint64_t *exit_after)
     if (c->pin_scalars[4]) *redo = 1;                           // (the header said so)
     if (*redo) c->pending.clear();
     if (exit_after) *exit_after = *reinterpret_cast<volatile uint64_t *>(c->pin_scalars + 12);
-    c->spec_density = (c->shard_end > c->shard_start) ? (double)c->last_M / (double)(c->shard_end - c->shard_start) : 0.0;
+    note_density(c, c->shard_end - c->shard_start);
     c->last_tags = c->n_hits;
-    c->last_dom_ms = 0.0f;
-    if (c->dom_timed && hipEventElapsedTime(&c->last_dom_ms, c->ev[3], c->ev[1]) != hipSuccess) c->ht[6] += 1.0;
+    read_dom_ms(c);
     return AM_OK;
 }
 

@@ -213,18 +213,20 @@ def run_stream_shards(lib, rate, iq, W, K, thr=7.0, pmf=True, dcblock=False):
     return np.concatenate(out)
 
 
-def run_stream_shards_in_flight(lib, rate, iq, W, K, thr=7.0, pmf=True, dcblock=False, small_cap=512, rx_time=()):
+def run_stream_shards_in_flight(lib, rate, iq, W, K, thr=7.0, pmf=True, dcblock=False, small_cap=512, rx_time=(), ctxs=None):
     """The same receiver with STEPS IN FLIGHT and the tables on the device, W ranks in ONE process: what
     air_modes/sharded.py::PipelinedShardedReceiver does over torch.distributed, through the C ABI alone.  Every rank has two
     contexts (steps alternate) and a carry word of its own; a step's messages lie side by side in one buffer (the all-gather is
     the layout); step k + 1 is scanned on every rank BEFORE step k is resolved; am_shard_resolve_submit composes the entry through
     all ranks' tables from the rank's carry word (cur_in) and leaves the step's last exit there (carry_out).  A flagged step (redo)
-    is repeated on the synchronous path by every rank, with its successor already scanned.  Returns (packets in (step, rank)
-    order, steps redone)."""
+    is repeated on the synchronous path by every rank, with its successor already scanned.  `ctxs`: reuse these contexts (a pair per
+    rank) and keep them open.  Returns (packets in (step, rank) order, steps redone)."""
     m = len(iq) // (W * K)
     assert m * W * K == len(iq)
     emulated = bool(getattr(lib, "emulated", False))
-    ctxs = [[_capi.Context(rate, thr, pmf, use_dcblock=dcblock, device=(-1 if emulated else 0), lib=lib) for _ in range(2)] for _ in range(W)]
+    keep = ctxs is not None
+    if not keep:
+        ctxs = [[_capi.Context(rate, thr, pmf, use_dcblock=dcblock, device=(-1 if emulated else 0), lib=lib) for _ in range(2)] for _ in range(W)]
     for pair in ctxs:
         for c in pair:
             for tag in rx_time:
@@ -291,10 +293,75 @@ def run_stream_shards_in_flight(lib, rate, iq, W, K, thr=7.0, pmf=True, dcblock=
             for r in range(W):
                 wr(carry[r], int(leave[W - 1]))
         out.extend(g[0] for g in got)
-    for pair in ctxs:
-        for c in pair:
-            c.close()
+    if not keep:
+        for pair in ctxs:
+            for c in pair:
+                c.close()
     return np.concatenate(out), redone
+
+
+def check_one_context_every_tail(lib, rate):
+    """Every kind of scan tail on the SAME two contexts, one after the other: steps in flight (deferred tail, entry composed on the
+    device, flag and exit word with the ticket), the gated stream, the block-level preamble, kept tags, steps in flight that are
+    redone on the synchronous path, and steps in flight once more.  Whatever one kind of tail left behind in a context would show in
+    the next: every leg is compared with the oracle or with a fresh context given the same calls."""
+    spc = int(rate / 2e6)
+    thr, pmf = 7.0, True
+    iq, _ = synth.synth_capture(rate, 20000 * spc, 6000.0, 3)
+    n = len(iq)
+    want = oracle.demod(iq, rate, thr, pmf)
+    assert len(want) >= 20
+    device = -1 if bool(getattr(lib, "emulated", False)) else 0
+    fresh = lambda: _capi.Context(rate, thr, pmf, device=device, lib=lib)
+    c0, c1 = fresh(), fresh()
+
+    def in_flight(small_cap):
+        return run_stream_shards_in_flight(lib, rate, iq, 1, 4, thr, pmf, small_cap=small_cap, ctxs=[[c0, c1]])
+
+    def gated_stream(c):
+        c.reset()
+        c.set_address_gate(1)
+        cuts = [0, n // 3, 2 * n // 3 + 7, n]
+        parts = [c.process_iq(iq[a:b], flush=(b == n)) for a, b in zip(cuts[:-1], cuts[1:])]
+        return np.concatenate(parts).tobytes(), c.address_gate_stats()
+
+    def block_preamble(c, bb, avg):
+        c.set_address_gate(0)
+        bursts, tags = c.preamble_work(bb, avg)
+        return u32(bursts).tobytes(), np.ascontiguousarray(tags).tobytes()
+
+    def kept_tags(c):
+        c.reset()
+        pk = c.process_iq(iq, flush=True, keep_tags=True)
+        bursts, tags = c.fetch_tags()
+        return pk, u32(bursts).tobytes(), np.ascontiguousarray(tags).tobytes()
+
+    # 1. steps in flight
+    got, redone = in_flight(512)
+    assert got.tobytes() == want.tobytes() and redone == 0, "leg 1: %d vs %d packets, %d steps redone" % (len(got), len(want), redone)
+    # 2. gated stream
+    ref = fresh()
+    g_want, g_got = gated_stream(ref), gated_stream(c0)
+    assert g_want[1]["taught"] >= 1 and g_want[1]["dropped"] >= 1, g_want[1]
+    assert g_got[0] == g_want[0], "leg 2: gated packets differ"
+    assert g_got[1] == g_want[1], "leg 2: gate statistics differ: %r vs %r" % (g_got[1], g_want[1])
+    # 3. block-level preamble
+    bb, avg = oracle.frontend(iq, spc, pmf)
+    assert block_preamble(c0, bb, avg) == block_preamble(ref, bb, avg), "leg 3: bursts / tags differ"
+    # 4. kept tags
+    k_want, k_got = kept_tags(ref), kept_tags(c0)
+    assert k_got[0].tobytes() == want.tobytes(), "leg 4: packets differ"
+    assert k_got[1:] == k_want[1:], "leg 4: kept bursts / tags differ"
+    ref.close()
+    # 5. steps in flight, flagged and redone on the synchronous path
+    got, redone = in_flight(1)
+    assert got.tobytes() == want.tobytes() and redone >= 1, "leg 5: %d vs %d packets, %d steps redone" % (len(got), len(want), redone)
+    # 6. ... and once more without
+    got, redone = in_flight(512)
+    assert got.tobytes() == want.tobytes() and redone == 0, "leg 6: %d vs %d packets, %d steps redone" % (len(got), len(want), redone)
+    c0.close()
+    c1.close()
+    return len(want)
 
 
 def check_stream_sharded(lib, rate, iq, W, K, thr=7.0, pmf=True, want=None, dcblock=False):

@@ -491,3 +491,9 @@ def test_steps_in_flight_over_w_ranks_in_one_process(emu_lib, rate, W, K, m, sma
     want = oracle.demod(iq, rate, rx_time=tags)
     assert len(want) > 20 and got.tobytes() == want.tobytes()
     assert (redone >= K - 1) if small_cap == 1 else (redone == 0)
+
+
+@pytest.mark.parametrize("rate", [8e6, 64e6])
+def test_one_context_every_tail(emu_lib, rate):
+    """Two contexts through every kind of scan tail in turn (pc.check_one_context_every_tail): nothing a tail was told survives it."""
+    assert pc.check_one_context_every_tail(emu_lib, rate) >= 20

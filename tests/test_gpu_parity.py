@@ -579,3 +579,9 @@ def test_steps_in_flight_over_w_ranks_on_device(hip_lib, oracle_mod, rate, W, K,
     want = oracle_mod.demod(iq, rate, rx_time=tags)
     assert len(want) > 50 and got.tobytes() == want.tobytes()
     assert (redone >= K - 1) if small_cap == 1 else (redone == 0)
+
+
+@pytest.mark.parametrize("rate", [8e6, 64e6])
+def test_one_context_every_tail_on_device(hip_lib, oracle_mod, rate):
+    """Two contexts through every kind of scan tail in turn on the GPU (pc.check_one_context_every_tail)."""
+    assert pc.check_one_context_every_tail(hip_lib, rate) >= 20

@@ -38,12 +38,41 @@ struct DevBuf {
 
 char g_create_err[256] = "";
 
-// What run_refine was last asked for (a speculative scan that met more candidates than its capacity is redone from this)
+// Which kernels a scan runs (scan_path; what am_last_frontend reports): none yet, the rate-generic kernels (dense bb / avg), the
+// tile kernel am_k_fe2 (dense bb: TEST builds only), the streaming front ends (am_k_fe3 / am_k_fe4: bitmap + sparse rows)
+enum ScanPath { PATH_NONE = 0, PATH_GENERIC = 1, PATH_TILE = 2, PATH_STREAM = 3 };
+// ... and which refinement goes behind them: chosen once, where the scan is set up
+enum RefineKind {
+    REFINE_GENERIC,       // am_k_refine over the detection kernel's segments; always reads its exact count back
+    REFINE_SPLIT,         // behind the tile kernel: positions -> energies -> per-candidate test (TEST builds only)
+    REFINE_LATE,          // behind am_k_fe4: am_k_gather_wg + am_k_refine_late on the rows the front end wrote
+    REFINE_LATE_ROWS,     // 64 Msps, AIRMODES_FUSED_REFINE=0 (TEST builds): the same, am_k_gather_wg<1> forms the rows from IQ
+    REFINE_SEG,           // 64 Msps: list + rows + refinement in one launch (am_k_refine_seg)
+};
+inline bool reads_bitmap(RefineKind k) { return k == REFINE_LATE || k == REFINE_LATE_ROWS || k == REFINE_SEG; }
+inline bool rows_from_iq(RefineKind k) { return k == REFINE_LATE_ROWS || k == REFINE_SEG; }
+
+// What run_refine is asked for (a speculative scan that met more candidates than its capacity is redone from this)
 struct RefineArgs {
     const float *bb = nullptr, *avg = nullptr;
     uint32_t nseg = 0, stride = 0;
-    int mode = 0;
+    RefineKind kind = REFINE_GENERIC;
     uint32_t end_j = 0xFFFFFFFFu;
+};
+
+// What the front half of a scan (run_front_and_candidates / run_candidates, run_refine) leaves for the tail (chain_prepare,
+// chain_finish) and for a redo with the exact count.  The context holds one: the resident scan (am_ctx::scan).
+struct Scan {
+    ScanPath path = PATH_NONE;         // which front end ran last (am_last_frontend; new_scan keeps it)
+    uint32_t M = 0;                    // flat records (pos, e, tgt, inavg, valid) -- or the capacity they were launched for,
+    const uint32_t *Mp = nullptr;      // ... with the count on the device (speculative launch); null: M is exact
+    bool jump_ready = false;           // the refinement already wrote the chain's successor array (am_k_cand / am_k_refine_*)
+    bool sparse = false;               // bb (ref.bb) exists only around candidates (streaming front end): burst extraction
+    const float *src = nullptr;        // ... recomputes from these samples, which must stay valid until the scan's hits are sliced
+    uint64_t src_abs0 = 0, src_abs1 = 0;
+    am_fe_layout fe;                   // streaming front end: the bitmap it left (am_fe_plan, through the launcher)
+    am_rows_args rows = {};            // ... and what forms the bb rows around candidates (64 Msps: from IQ, behind the front end)
+    RefineArgs ref;                    // dense bb / sparse rows, reference level, segments, refinement variant
 };
 
 // What the tail of a scan (chain_finish: walk, marking, extraction, slicing, completion ticket) is asked for, beyond the
@@ -76,6 +105,7 @@ struct am_ctx {
     double rate = 0.0;
     uint64_t rate_i = 0;
     int spc = 0;                  // int(rate / 2e6): what the front end runs at (rx_path.py:35)
+    float s1 = 0.0f, sL = 0.0f;   // float(1 / spc), float(1 / (48 spc)): the front ends' scale factors (rx_path.py:49, :54)
     int spc_hi = 0;               // samples per chip rounded UP: look-ahead sizes (= spc for a multiple of 2 MHz)
     bool frac = false;            // the rate is not a multiple of 2 MHz: rate-generic kernels, geometry from `geom`
     am_geom geom;                 // the preamble block's geometry in the reference's float arithmetic
@@ -99,14 +129,11 @@ struct am_ctx {
     // Speculative launches: the candidate count of a scan is only known on the device when its kernels
     // are enqueued.  Instead of a host round trip in the middle of the pipeline, the streaming path
     // launches for a capacity extrapolated from the previous scan (spec_cap) and lets the kernels clip
-    // to the device-side count (Mdev); the real count comes back with the results, and a scan whose
+    // to the device-side count (Scan::Mp); the real count comes back with the results, and a scan whose
     // count exceeded the capacity is redone with the exact count.
     bool allow_spec = true;       // (test builds: AIRMODES_NO_SPEC=1 disables)
-    bool spec_now = false;        // this scan was launched for a capacity
-    const uint32_t *Mdev = nullptr;
     double spec_density = 0.0;    // candidates per position, previous scan
     double spec_floor = 16384.0;  // slack added to the extrapolated capacity (AIRMODES_SPEC_FLOOR, tests)
-    RefineArgs ref;               // arguments of the last run_refine (for the redo)
     int use_dcblock = 0;          // a2: dc_blocker_cc(100*spc, False) in front of |.|^2 (rx_path.py:39-41)
     const float *zt_base[2] = {nullptr, nullptr};   // where the zero tail of bb / avg was last written
     uint64_t zt_n[2] = {0, 0};
@@ -128,25 +155,19 @@ struct am_ctx {
     struct Pending {
         bool active = false;      // a submitted batch awaits am_collect
         bool scanned = false;     // ... and it has a scan in flight (a ticket to wait for)
-        uint32_t seq = 0, M = 0, n_max = 0, j0 = 0, j1 = 0;
-        const uint32_t *Mp = nullptr;
+        uint32_t seq = 0, n_max = 0, j0 = 0, j1 = 0;
         TailReq req;              // what its tail was asked for (chain_collect; am_collect's redo)
         double T0 = 0.0;
     } pend;
     uint64_t rec_base = 0;        // absolute index of array coordinate 0 of the resident records (am_fetch_candidates)
     bool poison = false;          // (test builds: AIRMODES_POISON=1) NaN-fill the sparse bb / reference-level arrays before every scan
-    bool rows_from_iq = false;       // 64 Msps: the bb rows around candidates are formed from IQ behind the front end, not written by it (the scan in flight)
     bool fused_refine = true;        // 64 Msps (round 6): list + rows + refinement in one launch, the rows in LDS (am_k_refine_seg); test builds:
                                      // AIRMODES_FUSED_REFINE=0 keeps am_k_gather_wg<1> + am_k_refine_late with a maximum per row
     DevBuf bbmax;
-    am_rows_args rows = {};
     bool allow_stream = true;        // (test builds: AIRMODES_FE=2) keeps the tile kernel (am_k_fe2, dense bb) where the streaming one would run
-    // the scan whose records are resident: bb exists only around candidates (streaming front end), so burst
-    // extraction recomputes from these samples (they must stay valid until the scan's hits are sliced)
-    bool bb_sparse = false;
-    int last_fe = 0;              // which front end the last scan ran (am_last_frontend)
-    const float *scan_src = nullptr;
-    uint64_t scan_src_abs0 = 0, scan_src_abs1 = 0;
+    // the scan whose records are resident: assigned whole when a scan starts (new_scan), read by its tail -- in the same call, or
+    // in a later one (am_shard_scan then am_shard_resolve*, am_submit_iq then am_collect)
+    Scan scan;
     char err[256] = "";
 
     // "rx_time" stream tags still able to stamp a future preamble, ascending offsets (am_set_rx_time);
@@ -176,10 +197,6 @@ struct am_ctx {
     DevBuf src, bb, avg, cand_seg, inavg, blk_cnt, blk_off, pos, e, tgt, valid,
         jump, emit_idx, dcount, off_local, blk_tot2, blk_base2, energy, bits, seg_base,
         cblk_cnt, cblk_off, scalars, bursts, tags, packets, crc_pow, recs, cscratch, dc_m1, dc_y, wgmax;
-    uint32_t fe_vspan = 0, fe_nv = 0;  // streaming front end of the resident scan: array coordinates per workgroup, workgroups
-    uint32_t fe_lag = 0, fe_wbits = 32;  // ... its bitmap: positions behind (lag), per word
-    uint32_t fe_nwg = 0, fe_wpw = 0, fe_nwords = 0;   // ... front-end workgroups, bitmap words per workgroup, words in all
-    uint32_t fe_nlong = 0, fe_wps = 0;    // ... levelled segments (am_launch_fe3): workgroups with fe_wpw words (the others: fe_wps fewer); 0: all alike
     int fe_wgs_per_cu = 0;                // persistent front-end workgroups per CU (0: as many as fit; am_pipe: one fewer)
     DevBuf lb_dc, lb_mark;      // slots of the chained scans (am_chain_prefix): zero at allocation, tagged with lb_epoch
     uint32_t lb_epoch = 0;
@@ -193,9 +210,6 @@ struct am_ctx {
     std::vector<am_packet> pending;     // accepted packets not yet handed to the caller
     uint64_t last_tags = 0;
     uint32_t last_M = 0;
-    uint32_t chain_M = 0;               // records (or capacity) chain_prepare ran for
-    bool jump_ready = false;            // the refinement already wrote the chain's successor array (am_k_cand)
-    const uint32_t *chain_Mp = nullptr; // device-side count when chain_M is a capacity
 
     // time-sharded mode: the chunk whose bb/avg are resident
     uint64_t shard_base = 0, shard_start = 0, shard_end = 0, shard_total = 0;
@@ -372,6 +386,8 @@ int configure_rate(am_ctx *c, double rate)
     c->rate = rate;
     c->rate_i = rate_i;
     c->spc = spc;
+    c->s1 = (float)(1.0 / (double)spc);
+    c->sL = (float)(1.0 / (double)(AM_CHIPS_AVG * spc));
     c->frac = (double)spc * 2e6 != rate;
     c->spc_hi = c->frac ? spc + 1 : spc;
     c->geom = g;
@@ -474,61 +490,60 @@ int run_frontend(am_ctx *c, const float *src, uint64_t src_abs0, uint64_t src_ab
     a.spc = c->spc;
     a.use_pmf = c->use_pmf;
     a.tile = c->tile;
-    a.s1 = (float)(1.0 / (double)c->spc);                           // rx_path.py:49
-    a.sL = (float)(1.0 / (double)(AM_CHIPS_AVG * c->spc));          // rx_path.py:54
+    a.s1 = c->s1; a.sL = c->sL;
     HIPCHK(c, am_launch_frontend(a, c->stream));
     return AM_OK;
 }
 
-// Which kernels a scan of this context runs: 3 = the streaming front ends (am_k_fe3 / am_k_fe4: bitmap + sparse rows), 1 = the
-// rate-generic kernels (dense bb / avg), 2 = the tile kernel am_k_fe2 (dense bb) -- in TEST builds only (-DAM_WITH_TILE_KERNEL:
-// tests/gpu_variants, tests/emu; round 5: the product library no longer carries it nor the split refinement behind it).
+// Which kernels a scan of this context runs.  PATH_TILE exists in TEST builds only (-DAM_WITH_TILE_KERNEL: tests/gpu_variants,
+// tests/emu; round 5: the product library no longer carries am_k_fe2 nor the split refinement behind it).
 // dense_wanted: the caller wants bb / avg as whole arrays (block-level am_frontend_work).
-static int scan_path(const am_ctx *c, bool dense_wanted)
+static ScanPath scan_path(const am_ctx *c, bool dense_wanted)
 {
-    if (c->force_generic || c->frac) return 1;
-    if (!dense_wanted && c->allow_stream && am_fe4_supported(c->spc)) return 3;
+    if (c->force_generic || c->frac) return PATH_GENERIC;    // (fractional samples per chip: the rate-generic kernels)
+    if (!dense_wanted && c->allow_stream && am_fe4_supported(c->spc)) return PATH_STREAM;
 #if AM_WITH_TILE_KERNEL
-    if (am_fe2_tile(c->spc)) return 2;
+    if (am_fe2_tile(c->spc)) return PATH_TILE;
 #endif
-    return 1;
+    return PATH_GENERIC;
 }
 
-// Scan of the per-segment candidate counts and read-back of the total; then either the
-// refinement kernel (generic path: candidates only) or the gather of the records the fused
-// kernel already produced.  Leaves the flat records (pos, e, tgt, inavg, valid) on the device.
-int run_refine(am_ctx *c, const RefineArgs a, uint32_t *M_out, uint32_t spec_cap = 0)
+// A scan starts: whatever the one before left for its tail is gone (which front end ran last stays on record until one runs again)
+Scan &new_scan(am_ctx *c)
 {
-    const auto [bb, avg, nseg, seg_stride, mode, end_j] = a;
-    *M_out = 0;
-    c->spec_now = false;
-    c->Mdev = nullptr;
-    c->jump_ready = false;
+    const ScanPath ran = c->scan.path;
+    return c->scan = Scan{ran};
+}
+
+// Scan of the per-segment candidate counts and read-back of the total -- or, spec_cap != 0 and not the generic kernels, a launch
+// for that capacity --, then the refinement sc.ref asks for.  Leaves the flat records on the device and their number in sc.
+int run_refine(am_ctx *c, Scan &sc, uint32_t spec_cap = 0)
+{
+    const auto [bb, avg, nseg, seg_stride, kind, end_j] = sc.ref;
+    const am_fe_layout &fe = sc.fe;
+    sc.M = 0; sc.Mp = nullptr; sc.jump_ready = false;
     if (nseg == 0) return AM_OK;
     if (int rcs = ensure_scalars(c); rcs != AM_OK) return rcs;
+    const bool spec = spec_cap && kind != REFINE_GENERIC;
     const uint32_t *count_ptr = (const uint32_t *)c->blk_off.p + nseg;       // device-side total
-    if (mode == 3) {
+    if (reads_bitmap(kind)) {
         // streaming front end: the flat list is laid out from the per-workgroup counts by the gather kernel itself, which also
         // leaves the total (blk_off[0]); only a scan that must know its count up front adds the counts first
         count_ptr = (const uint32_t *)c->blk_off.p;
-        if (!(spec_cap && mode >= 2)) {
-            ENSURE(c, c->seg_base, ((size_t)c->fe_nwg + 2) * sizeof(uint32_t));
-            HIPCHK(c, am_launch_scan_u32((uint32_t *)c->blk_cnt.p, (uint32_t *)c->seg_base.p, c->fe_nwg, c->stream));
-            count_ptr = (const uint32_t *)c->seg_base.p + c->fe_nwg;
+        if (!spec) {
+            ENSURE(c, c->seg_base, ((size_t)fe.nwg + 2) * sizeof(uint32_t));
+            HIPCHK(c, am_launch_scan_u32((uint32_t *)c->blk_cnt.p, (uint32_t *)c->seg_base.p, fe.nwg, c->stream));
+            count_ptr = (const uint32_t *)c->seg_base.p + fe.nwg;
         }
     } else
         HIPCHK(c, am_launch_scan_u32((uint32_t *)c->blk_cnt.p, (uint32_t *)c->blk_off.p, nseg, c->stream));
-    c->ref = a;
     uint32_t M = 0;
     const uint32_t *Mp = nullptr;
-    if (spec_cap && mode >= 2) {
+    if (spec) {
         M = spec_cap;                                        // capacity; the kernels clip to *Mp
         Mp = count_ptr;                                      // (streaming front end: written by the gather kernel below)
-        c->spec_now = true;
-        c->Mdev = Mp;
     } else {
-        HIPCHK(c, hipMemcpyAsync(&M, count_ptr, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                 c->stream));
+        HIPCHK(c, hipMemcpyAsync(&M, count_ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     if (M) {
@@ -537,33 +552,32 @@ int run_refine(am_ctx *c, const RefineArgs a, uint32_t *M_out, uint32_t spec_cap
         ENSURE(c, c->tgt, ((size_t)M + 1) * sizeof(uint32_t));
         ENSURE(c, c->inavg, ((size_t)M + 1) * sizeof(float));
         ENSURE(c, c->valid, (size_t)M + 1);
-        if (mode == 3 && c->rows_from_iq && c->fused_refine) {
+        if (kind != REFINE_GENERIC) ENSURE(c, c->jump, ((size_t)M + 1) * sizeof(uint32_t));   // (they write the chain's successors)
+        switch (kind) {
+        case REFINE_SEG:
             // 64 Msps: flat positions, bb rows (in LDS), late-peak decisions, quiet zones, records and the chain's successors in ONE
             // launch, one workgroup per front-end workgroup (am_k_refine_seg)
-            ENSURE(c, c->jump, ((size_t)M + 1) * sizeof(uint32_t));
 #if defined(AM_TEST_KNOBS)
-            if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: am_k_refine_seg, %u segments of %u words, capacity %u\n", c->fe_nwg, c->fe_wpw, M);
+            if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: am_k_refine_seg, %u segments of %u words, capacity %u\n", fe.nwg, fe.words_per_wg(), M);
 #endif
-            HIPCHK(c, am_launch_refine_seg((uint32_t *)c->bits.p, (uint32_t *)c->blk_cnt.p, (const float *)c->wgmax.p, c->fe_nwg, c->fe_nlong,
-                                           c->fe_wpw, c->fe_wps, c->fe_nwords, M, c->fe_lag, c->fe_wbits, c->fe_vspan, c->fe_nv, c->rows, avg, c->thr_lin, end_j,
-                                           (uint32_t *)c->pos.p, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p, (float *)c->inavg.p,
-                                           (uint8_t *)c->valid.p, (uint32_t *)c->jump.p, (uint32_t *)c->blk_off.p, c->stream));
-            c->jump_ready = true;
-        } else if (mode == 3) {
+            HIPCHK(c, am_launch_refine_seg((uint32_t *)c->bits.p, (uint32_t *)c->blk_cnt.p, (const float *)c->wgmax.p, fe, M, sc.rows, avg,
+                                           c->thr_lin, end_j, (uint32_t *)c->pos.p, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p,
+                                           (float *)c->inavg.p, (uint8_t *)c->valid.p, (uint32_t *)c->jump.p, (uint32_t *)c->blk_off.p,
+                                           c->stream));
+            break;
+        case REFINE_LATE:
+        case REFINE_LATE_ROWS:
             // streaming front end: candidates arrive as a bitmap; flat positions, then late-peak decisions, quiet zones,
             // records and the chain's successors in one launch (am_k_refine_late)
-            HIPCHK(c, am_launch_gather_wg((uint32_t *)c->bits.p, (uint32_t *)c->blk_cnt.p, c->fe_nwg, c->fe_wpw, c->fe_nwords, M,
-                                          c->fe_lag, c->fe_wbits, (uint32_t *)c->pos.p, (uint32_t *)c->blk_off.p, c->stream,
-                                          c->rows_from_iq ? &c->rows : nullptr));
-            ENSURE(c, c->jump, ((size_t)M + 1) * sizeof(uint32_t));
+            HIPCHK(c, am_launch_gather_wg((uint32_t *)c->bits.p, (uint32_t *)c->blk_cnt.p, fe, M, (uint32_t *)c->pos.p,
+                                          (uint32_t *)c->blk_off.p, c->stream, kind == REFINE_LATE_ROWS ? &sc.rows : nullptr));
             HIPCHK(c, am_launch_refine_late(bb, avg, (uint32_t *)c->pos.p, M, c->spc, c->thr_lin, end_j, (uint32_t *)c->e.p,
                                             (uint32_t *)c->tgt.p, (float *)c->inavg.p, (uint8_t *)c->valid.p,
-                                            (uint32_t *)c->jump.p, c->stream, Mp, (const float *)c->wgmax.p, c->fe_vspan,
-                                            c->fe_nv, c->rows_from_iq ? c->rows.bb_max : nullptr));
-            c->jump_ready = true;
-        }
+                                            (uint32_t *)c->jump.p, c->stream, Mp, (const float *)c->wgmax.p, fe,
+                                            kind == REFINE_LATE_ROWS ? sc.rows.bb_max : nullptr));
+            break;
+        case REFINE_SPLIT: {
 #if AM_WITH_TILE_KERNEL
-        else if (mode >= 2) {
             // split refinement behind the tile kernel: positions -> energy per reachable position -> per-candidate test
             const uint32_t nb = (M + 2047u) / 2048u;
             const uint64_t ebound = std::min<uint64_t>((uint64_t)M * (uint64_t)(c->spc + 1), (uint64_t)M + 0xFFFFFFFFull);
@@ -582,21 +596,25 @@ int run_refine(am_ctx *c, const RefineArgs a, uint32_t *M_out, uint32_t spec_cap
                                              c->stream, Mp));
             HIPCHK(c, am_launch_energy(bb, (uint32_t *)c->pos.p, (uint32_t *)c->dcount.p, (uint32_t *)c->off_local.p,
                                        nullptr, M, c->spc, (double *)c->energy.p, c->stream, Mp));
-            ENSURE(c, c->jump, ((size_t)M + 1) * sizeof(uint32_t));
             HIPCHK(c, am_launch_cand(bb, avg, (uint32_t *)c->pos.p, (uint32_t *)c->dcount.p,
                                      (uint32_t *)c->off_local.p, nullptr, (double *)c->energy.p, M,
                                      c->spc, c->thr_lin, end_j, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p,
                                      (float *)c->inavg.p, (uint8_t *)c->valid.p, (uint32_t *)c->jump.p, c->stream, Mp));
-            c->jump_ready = true;
-        }
+            break;
+#else
+            return fail(c, AM_EINVAL, "internal: no kernel for this refinement");
 #endif
-        else
+        }
+        case REFINE_GENERIC:
             HIPCHK(c, am_launch_refine(bb, avg, c->geom, c->thr_lin, (uint32_t *)c->cand_seg.p, seg_stride,
                                        (uint32_t *)c->blk_off.p, nseg, M, (uint32_t *)c->pos.p,
                                        (uint32_t *)c->e.p, (uint32_t *)c->tgt.p, (float *)c->inavg.p,
                                        (uint8_t *)c->valid.p, c->stream));
+            break;
+        }
+        sc.jump_ready = kind != REFINE_GENERIC;
     }
-    *M_out = M;
+    sc.M = M; sc.Mp = Mp;
     return AM_OK;
 }
 
@@ -610,11 +628,10 @@ uint32_t spec_capacity(const am_ctx *c, uint32_t npos)
 }
 
 // Candidate detection + refinement over positions [j0, j1) of existing device arrays bb/avg
-// (block-level entry point: the generic detection kernel).
-int run_candidates(am_ctx *c, const float *bb, const float *avg, uint32_t j0, uint32_t j1, uint32_t *M_out)
+// (block-level entry point: the generic detection kernel).  The result is the context's resident scan.
+int run_candidates(am_ctx *c, const float *bb, const float *avg, uint32_t j0, uint32_t j1)
 {
-    *M_out = 0;
-    c->bb_sparse = false;
+    Scan &sc = new_scan(c);
     if (j1 <= j0) return AM_OK;
     const uint32_t nblk = (uint32_t)(((uint64_t)(j1 - j0) + AM_DET_PER_BLOCK - 1) / AM_DET_PER_BLOCK);
     ENSURE(c, c->cand_seg, (size_t)nblk * AM_DET_PER_BLOCK * sizeof(uint32_t));
@@ -622,88 +639,64 @@ int run_candidates(am_ctx *c, const float *bb, const float *avg, uint32_t j0, ui
     ENSURE(c, c->blk_off, ((size_t)nblk + 1) * sizeof(uint32_t));
     HIPCHK(c, am_launch_detect(bb, avg, j0, j1, c->geom, c->thr_lin, (uint32_t *)c->cand_seg.p,
                                (uint32_t *)c->blk_cnt.p, nblk, c->stream));
-    return run_refine(c, {bb, avg, nblk, AM_DET_PER_BLOCK, 0}, M_out);
+    sc.ref = {bb, avg, nblk, AM_DET_PER_BLOCK, REFINE_GENERIC};
+    return run_refine(c, sc);
 }
 
 // IQ -> bb, avg and the refined candidate records for positions [j0, j1): the fused
-// specialisation when this samples-per-chip has one, the generic kernel pair otherwise.
+// specialisation when this samples-per-chip has one, the generic kernel pair otherwise.  The result is the context's resident scan.
 int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uint64_t src_abs1, uint64_t out_abs0,
-                             uint64_t out_n, float *bb, float *avg, uint32_t j0, uint32_t j1, uint32_t *M_out,
-                             bool may_speculate = false)
+                             uint64_t out_n, float *bb, float *avg, uint32_t j0, uint32_t j1, bool may_speculate = false)
 {
-    *M_out = 0;
-    c->spec_now = false;
-    c->Mdev = nullptr;
-    c->bb_sparse = false;
-    const int path = scan_path(c, avg != nullptr);           // (fractional samples per chip: the rate-generic kernels)
+    const ScanPath path = scan_path(c, avg != nullptr);
     HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-    c->last_fe = path == 1 ? 1 : 2;
-    if (path == 1) {
+    if (path == PATH_GENERIC) {
         if (!avg) return fail(c, AM_EINVAL, "internal: the rate-generic kernels need the dense reference-level array");
         int rc = run_frontend(c, src, src_abs0, src_abs1, out_abs0, out_n, bb, avg);
         if (rc != AM_OK) return rc;
         HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
         c->dom_timed = true;
-        return run_candidates(c, bb, avg, j0, j1, M_out);
+        rc = run_candidates(c, bb, avg, j0, j1);
+        c->scan.path = path;
+        return rc;
     }
-    c->scan_src = src; c->scan_src_abs0 = src_abs0; c->scan_src_abs1 = src_abs1;
-    if (path == 3) {
-        // streaming kernel: candidate bitmap + per-(step, wave) counts; bb and the reference level only around candidates
-        const unsigned ns = am_fe4_steps((long long)out_n, c->spc);
-        const unsigned wps = am_fe4_words(c->spc) * am_fe4_waves(c->spc);     // bitmap words per step
-        ENSURE(c, c->bits, ((size_t)ns * wps + 64) * sizeof(uint32_t));
-        ENSURE(c, c->blk_cnt, ((size_t)ns + 8) * sizeof(uint32_t));           // candidates per front-end workgroup
-        ENSURE(c, c->blk_off, 16 * sizeof(uint32_t));                          // [0]: their total (am_k_gather_wg)
+    Scan &sc = new_scan(c);
+    sc.path = path; sc.src = src; sc.src_abs0 = src_abs0; sc.src_abs1 = src_abs1;
+    const uint32_t end_j = (uint32_t)std::min<uint64_t>(src_abs1 > out_abs0 ? src_abs1 - out_abs0 : 0, 0xFFFFFFFFull);
+    if (path == PATH_STREAM) {
+        // streaming kernel: candidate bitmap + per-workgroup counts; bb and the reference level only around candidates
+        const am_fe_layout sizes = am_fe_plan(c->spc, (long long)out_n, 1, false);    // (steps and words do not depend on the grid)
+        ENSURE(c, c->bits, ((size_t)sizes.nwords() + 64) * sizeof(uint32_t));
+        ENSURE(c, c->blk_cnt, ((size_t)sizes.nsteps + 8) * sizeof(uint32_t));    // candidates per front-end workgroup
+        ENSURE(c, c->blk_off, 16 * sizeof(uint32_t));                             // [0]: their total (am_k_gather_wg)
         ENSURE(c, c->avg, (out_n + zero_pad(c->spc_hi)) * sizeof(float));
-        ENSURE(c, c->wgmax, ((size_t)ns + 8) * sizeof(float));
-        unsigned nsteps = 0, spw = 1, nlong = 0;
+        ENSURE(c, c->wgmax, ((size_t)sizes.nsteps + 8) * sizeof(float));
         if (c->poison) {
             // test aid (AIRMODES_POISON=1): whatever the sparse arrays are read for must have been written by this scan
             HIPCHK(c, hipMemsetAsync(bb, 0xFF, out_n * sizeof(float), c->stream));
             HIPCHK(c, hipMemsetAsync(c->avg.p, 0xFF, out_n * sizeof(float), c->stream));
         }
-        // 64 Msps (a bitmap word = one 32-sample chip, lag 288): the bb rows around candidates are formed from the samples by
-        // am_k_gather_wg, not written by the front end (~42 MB of stores per 64 M samples that the dominant kernel does not make)
-        c->rows_from_iq = am_fe4_unit(c->spc) == 32 && am_fe4_lag(c->spc) == 288;
-        c->rows.iq = c->rows_from_iq ? src : nullptr;
-        c->rows.src_abs0 = (long long)src_abs0; c->rows.src_abs1 = (long long)src_abs1; c->rows.out_abs0 = (long long)out_abs0;
-        c->rows.out_n = (long long)out_n; c->rows.bb_sparse = bb; c->rows.use_pmf = c->use_pmf;
-        c->rows.bb_max = nullptr;
-        if (c->rows_from_iq && !c->fused_refine) {
+        // 64 Msps (a bitmap word = one 32-sample chip, lag 288): the bb rows around candidates are formed from the samples behind
+        // the front end, not written by it (~42 MB of stores per 64 M samples that the dominant kernel does not make) -- by
+        // am_k_refine_seg, which can place segments of two lengths, or (test builds) by am_k_gather_wg
+        const RefineKind kind = !(sizes.wbits == 32 && sizes.lag == 288) ? REFINE_LATE : c->fused_refine ? REFINE_SEG : REFINE_LATE_ROWS;
+        sc.rows = {rows_from_iq(kind) ? src : nullptr, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0, (long long)out_n,
+                   bb, nullptr, c->use_pmf, c->s1};
+        if (kind == REFINE_LATE_ROWS) {
             // one float per array chip: the largest bb of every row formed (am_k_refine_late: whole chips of a quiet zone)
             ENSURE(c, c->bbmax, ((size_t)(out_n / 32) + 64) * sizeof(float));
-            c->rows.bb_max = (float *)c->bbmax.p;
+            sc.rows.bb_max = (float *)c->bbmax.p;
             if (c->poison) HIPCHK(c, hipMemsetAsync(c->bbmax.p, 0xFF, ((size_t)(out_n / 32) + 64) * sizeof(float), c->stream));
         }
-        c->rows.s1 = (float)(1.0 / (double)c->spc);
-        HIPCHK(c, am_launch_fe4(c->spc, src, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0, (long long)out_n,
-                                c->rows_from_iq ? nullptr : bb,
-                                (float *)c->avg.p, j0, j1, c->use_pmf, (float)(1.0 / (double)c->spc),
-                                (float)(1.0 / (double)(AM_CHIPS_AVG * c->spc)), c->thr_lin, (uint32_t *)c->bits.p,
-                                (uint32_t *)c->blk_cnt.p, (float *)c->wgmax.p, &nsteps, &spw, c->stream, c->fe_wgs_per_cu,
-                                (c->rows_from_iq && c->fused_refine) ? &nlong : nullptr));      // (levelled segments: what am_k_refine_seg can place)
-        c->fe_vspan = spw * am_fe4_tile(c->spc);
-        c->fe_nv = (nsteps + spw - 1) / spw;
-        c->fe_nlong = 0;
-        c->fe_wps = wps;
-        if (nlong && spw > 1) {
-            // nlong workgroups of spw steps, then workgroups of spw - 1
-            const unsigned rest = nsteps > nlong * spw ? nsteps - nlong * spw : 0u;
-            c->fe_nv = nlong + (rest + (spw - 1) - 1) / (spw - 1);
-            c->fe_nlong = nlong;
-        }
-        c->fe_lag = am_fe4_lag(c->spc);
-        c->fe_wbits = am_fe4_unit(c->spc);
-        c->fe_nwg = c->fe_nv;
-        c->fe_wpw = spw * wps;
-        c->fe_nwords = nsteps * wps;
+        const am_fe_stream_req r = {src, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0, (long long)out_n,
+                                    rows_from_iq(kind) ? nullptr : bb, (float *)c->avg.p, j0, j1, c->use_pmf, c->s1, c->sL, c->thr_lin,
+                                    (uint32_t *)c->bits.p, (uint32_t *)c->blk_cnt.p, (float *)c->wgmax.p};
+        HIPCHK(c, am_launch_fe4(c->spc, r, &sc.fe, c->stream, c->fe_wgs_per_cu, kind == REFINE_SEG));
         HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
         c->dom_timed = true;
-        c->bb_sparse = true;
-        c->last_fe = 3;
-        const uint64_t endj3 = src_abs1 > out_abs0 ? src_abs1 - out_abs0 : 0;
-        return run_refine(c, {bb, (const float *)c->avg.p, c->fe_nwg, 0, 3, (uint32_t)std::min<uint64_t>(endj3, 0xFFFFFFFFull)}, M_out,
-                          may_speculate ? spec_capacity(c, j1 - j0) : 0u);
+        sc.sparse = true;
+        sc.ref = {bb, (const float *)c->avg.p, sc.fe.nwg, 0, kind, end_j};
+        return run_refine(c, sc, may_speculate ? spec_capacity(c, j1 - j0) : 0u);
     }
 #if AM_WITH_TILE_KERNEL
     const unsigned T2 = am_fe2_tile(c->spc);
@@ -721,14 +714,12 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
         avg_sparse = (float *)c->avg.p;
     }
     HIPCHK(c, am_launch_fe2(c->spc, src, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0,
-                            (long long)out_n, bb, avg, j0, j1, c->use_pmf, (float)(1.0 / (double)c->spc),
-                            (float)(1.0 / (double)(AM_CHIPS_AVG * c->spc)), c->thr_lin, (uint32_t *)c->cand_seg.p,
+                            (long long)out_n, bb, avg, j0, j1, c->use_pmf, c->s1, c->sL, c->thr_lin, (uint32_t *)c->cand_seg.p,
                             avg_sparse, (uint32_t *)c->blk_cnt.p, &nt, &tl, c->stream));
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     c->dom_timed = true;
-    const uint64_t endj = src_abs1 > out_abs0 ? src_abs1 - out_abs0 : 0;
-    return run_refine(c, {bb, avg_sparse ? avg_sparse : avg, nt, tl, 2, (uint32_t)std::min<uint64_t>(endj, 0xFFFFFFFFull)}, M_out,
-                      may_speculate && avg_sparse ? spec_capacity(c, j1 - j0) : 0u);
+    sc.ref = {bb, avg_sparse ? avg_sparse : avg, nt, tl, REFINE_SPLIT, end_j};
+    return run_refine(c, sc, may_speculate && avg_sparse ? spec_capacity(c, j1 - j0) : 0u);
 #else
     return fail(c, AM_EINVAL, "internal: no kernel for this scan");
 #endif
@@ -805,23 +796,23 @@ int gate_commit(am_ctx *c, uint32_t n)
 }
 
 // Greedy chain, part 1 (independent of where the scan starts): successor array and per-block exits
-// over the M flat records (M may be a capacity, with the device-side count in Mp).
-int chain_prepare(am_ctx *c, uint32_t M, bool want_last, const uint32_t *Mp = nullptr)
+// over the resident scan's flat records (their number may be a capacity, with the device-side count in Mp).
+int chain_prepare(am_ctx *c, bool want_last)
 {
-    c->chain_M = M;
-    c->chain_Mp = Mp;
+    const uint32_t M = c->scan.M;
+    const uint32_t *Mp = c->scan.Mp;
     if (M == 0) return AM_OK;
     const size_t stride = (size_t)M + 1;
     ENSURE(c, c->jump, stride * sizeof(uint32_t));
     if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
     ENSURE(c, c->cscratch, am_chain_scratch_bytes(M));
     HIPCHK(c, am_launch_chain_prepare((uint32_t *)c->pos.p, (uint32_t *)c->tgt.p, M, (uint32_t *)c->jump.p,
-                                      (uint32_t *)c->cscratch.p, want_last ? 1 : 0, c->stream, Mp, c->jump_ready ? 1 : 0));
+                                      (uint32_t *)c->cscratch.p, want_last ? 1 : 0, c->stream, Mp, c->scan.jump_ready ? 1 : 0));
     return AM_OK;
 }
 
-// The part of chain_finish behind the completion ticket: counts, resume position, accepted packets.
-int chain_collect(am_ctx *c, const TailReq &req, uint32_t M, const uint32_t *Mp, uint32_t n_max, uint32_t *final_cur)
+// The part of chain_finish behind the completion ticket: counts, resume position, accepted packets (of the resident scan).
+int chain_collect(am_ctx *c, const TailReq &req, uint32_t n_max, uint32_t *final_cur)
 {
     c->tail_synced = true;
     if (c->pin_scalars[5]) {
@@ -829,10 +820,10 @@ int chain_collect(am_ctx *c, const TailReq &req, uint32_t M, const uint32_t *Mp,
         (void)hipMemsetAsync((uint32_t *)c->scalars.p + 9, 0, sizeof(uint32_t), c->stream);
         return fail(c, AM_EHIP, "a chained scan on the device timed out (a workgroup never published its count)");
     }
-    if (Mp) {
+    if (c->scan.Mp) {
         // launched for a capacity: now the real candidate count is known
         c->last_M = c->pin_scalars[2];
-        if (c->pin_scalars[2] > M) return AM_RETRY_EXACT;    // capacity too small: results are incomplete
+        if (c->pin_scalars[2] > c->scan.M) return AM_RETRY_EXACT;    // capacity too small: results are incomplete
     }
     const uint32_t n_emit = c->pin_scalars[0];
     *final_cur = c->pin_scalars[1];
@@ -862,16 +853,17 @@ int chain_collect(am_ctx *c, const TailReq &req, uint32_t M, const uint32_t *Mp,
 
 // Greedy chain, part 2: mark the candidates the scan visits when it starts at req.cur0, then extract
 // and slice the hits (e <= emit_max, first-stage position in [own_lo, own_hi)).  Everything the caller decides is in
-// `req`; the rest is the resident scan (chain_prepare's records, the samples they were formed from).
+// `req`; the rest is the resident scan (its records, its dense bb or the samples they were formed from).
 // keep_bursts (block-level scan): fills h_tags + h_bursts.  Otherwise (streaming / sharded scan) the tags
 // stay on the device and the accepted packets go straight from pinned memory to `pending`.
-int chain_finish(am_ctx *c, const float *bb, const TailReq &req, uint32_t *final_cur)
+int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
 {
     const uint32_t cur0 = req.cur0, emit_max = req.emit_max;
     const uint64_t base_abs = req.base_abs;
     const bool keep_bursts = req.keep_bursts, gate = req.gate;
-    const uint32_t M = c->chain_M;
-    const uint32_t *Mp = c->chain_Mp;
+    const Scan &sc = c->scan;
+    const uint32_t M = sc.M;
+    const uint32_t *Mp = sc.Mp;
     c->h_packets.clear();
     c->h_tags.clear();
     c->h_bursts.clear();
@@ -920,10 +912,10 @@ int chain_finish(am_ctx *c, const float *bb, const TailReq &req, uint32_t *final
     // (the slicing waves write the accepted packets straight to the pinned array.  Routing them through device memory
     // and one coalesced copy in the ticket kernel was tried: the extraction kernel did not get faster and the copy
     // added 13 us to the ticket.)
-    if (c->bb_sparse && !keep_bursts)
+    if (sc.sparse && !keep_bursts)
         // bb exists only around the candidates: the 240 soft chips of a hit are recomputed from the scan's samples
-        HIPCHK(c, am_launch_extract_slice_iq(c->scan_src, (long long)c->scan_src_abs0, (long long)c->scan_src_abs1,
-                                             c->use_pmf, (float)(1.0 / (double)c->spc), (const float *)c->inavg.p, c->spc,
+        HIPCHK(c, am_launch_extract_slice_iq(sc.src, (long long)sc.src_abs0, (long long)sc.src_abs1,
+                                             c->use_pmf, c->s1, (const float *)c->inavg.p, c->spc,
                                              (const uint4 *)c->emit_idx.p, n_ptr, n_max, (uint32_t *)c->pos.p,
                                              (uint32_t *)c->e.p, base_abs, c->rate_i, (const am_time_tag *)c->tt_dev.p,
                                              (uint32_t)c->tt.size(), keep_dev ? (float *)c->bursts.p : nullptr,
@@ -931,7 +923,7 @@ int chain_finish(am_ctx *c, const float *bb, const TailReq &req, uint32_t *final
                                              c->pin_packets, (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp,
                                              c->fix_bits, gate ? 1 : 0));
     else
-    HIPCHK(c, am_launch_extract_slice(bb, (const float *)c->inavg.p, c->spc, c->frac ? (const int *)c->chip_idx.p : nullptr,
+    HIPCHK(c, am_launch_extract_slice(sc.ref.bb, (const float *)c->inavg.p, c->spc, c->frac ? (const int *)c->chip_idx.p : nullptr,
                                       c->geom.hist0, (const uint4 *)c->emit_idx.p, n_ptr, n_max,
                                       (uint32_t *)c->pos.p, (uint32_t *)c->e.p, base_abs, req.e_off, c->rate_i,
                                       (const am_time_tag *)c->tt_dev.p, (uint32_t)c->tt.size(),
@@ -954,20 +946,20 @@ int chain_finish(am_ctx *c, const float *bb, const TailReq &req, uint32_t *final
     c->total_pending = true;
     if (req.defer && !keep_bursts) {
         c->pend.scanned = true;
-        c->pend.seq = seq; c->pend.M = M; c->pend.Mp = Mp; c->pend.n_max = n_max;
+        c->pend.seq = seq; c->pend.n_max = n_max;
         c->pend.req = req;
         return AM_DEFERRED;
     }
     const double TS = am_now_us();
     HIPCHK(c, wait_for_ticket(c, seq));
     c->ht[5] += am_now_us() - TS;
-    return chain_collect(c, req, M, Mp, n_max, final_cur);
+    return chain_collect(c, req, n_max, final_cur);
 }
 
-int run_chain_and_slice(am_ctx *c, const float *bb, uint32_t M, const TailReq &req, uint32_t *final_cur)
+int run_chain_and_slice(am_ctx *c, const TailReq &req, uint32_t *final_cur)
 {
-    int rc = chain_prepare(c, M, false, c->spec_now ? c->Mdev : nullptr);
-    return rc != AM_OK ? rc : chain_finish(c, bb, req, final_cur);    // (no candidate: chain_finish leaves empty results)
+    int rc = chain_prepare(c, false);
+    return rc != AM_OK ? rc : chain_finish(c, req, final_cur);        // (no candidate: chain_finish leaves empty results)
 }
 
 void collect_accepted(am_ctx *c)
@@ -1081,7 +1073,7 @@ int hand_out_tags(am_ctx *c, float *bursts, am_tag *tags, uint64_t cap, uint64_t
 bool resolve_plan(const am_ctx *c, const am_shard_exit *msgs, uint32_t world, uint32_t rank, uint32_t msg_cap, TailReq &req)
 {
     uint64_t em = 0;
-    if (c->chain_M == 0 || (!c->shard_more && (!flush_limits(c, c->shard_total, &em) || em < c->shard_base))) return false;
+    if (c->scan.M == 0 || (!c->shard_more && (!flush_limits(c, c->shard_total, &em) || em < c->shard_base))) return false;
     req = TailReq();
     req.emit_max = c->shard_more ? 0xFFFFFFFEu : (uint32_t)std::min<uint64_t>(em - c->shard_base, 0xFFFFFFFEu);
     req.base_abs = c->shard_base;
@@ -1456,7 +1448,7 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         }
         if (fsrc_abs0 > need0) return fail(c, AM_EINVAL, "internal: stream history was not carried");
         const uint64_t pad = zero_pad(c->spc_hi);
-        const bool generic = scan_path(c, false) == 1;
+        const bool generic = scan_path(c, false) == PATH_GENERIC;
         ENSURE(c, c->bb, (out_n + pad) * sizeof(float));
         float *bb = (float *)c->bb.p, *avg = nullptr;
         ZERO_TAIL(c, 0, bb, out_n, pad);
@@ -1466,9 +1458,8 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
             ZERO_TAIL(c, 1, avg, out_n, pad);
         }
         const uint32_t j0 = (uint32_t)(P0 - out_abs0), j1 = (uint32_t)(P1 - out_abs0);
-        uint32_t M = 0;
         const double T1 = am_now_us();
-        int rc = run_front_and_candidates(c, fsrc, fsrc_abs0, S1, out_abs0, out_n, bb, avg, j0, j1, &M, true);
+        int rc = run_front_and_candidates(c, fsrc, fsrc_abs0, S1, out_abs0, out_n, bb, avg, j0, j1, true);
         if (rc != AM_OK) return rc;
         const double T2 = am_now_us();
         c->ht[0] += T1 - T0; c->ht[1] += T2 - T1;
@@ -1481,22 +1472,22 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         req.defer = submit;
         req.gate = c->gate_mode != 0;                       // these are the scans that hand out packets
         uint32_t fin = req.cur0;
-        rc = run_chain_and_slice(c, bb, M, req, &fin);
+        rc = run_chain_and_slice(c, req, &fin);
         c->ht[2] += am_now_us() - T2;
         if (rc == AM_DEFERRED) {
-            c->pend.active = true;                          // (chain_finish filled in scanned / seq / M / Mp / n_max / req)
+            c->pend.active = true;                          // (chain_finish filled in scanned / seq / n_max / req)
             c->pend.j0 = j0; c->pend.j1 = j1; c->pend.T0 = T0;
             return AM_OK;
         }
         if (rc == AM_RETRY_EXACT) {
 #if defined(AM_TEST_KNOBS)
-            if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: capacity %u < %u candidates, scan redone\n", M, c->last_M);
+            if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: capacity %u < %u candidates, scan redone\n", c->scan.M, c->last_M);
 #endif
             // more candidates than the capacity this scan was launched for: redo the refinement and
             // the chain with the exact count (the fused kernel's outputs are still in place)
-            rc = run_refine(c, c->ref, &M);
+            rc = run_refine(c, c->scan);
             if (rc != AM_OK) return rc;
-            rc = run_chain_and_slice(c, bb, M, req, &fin);
+            rc = run_chain_and_slice(c, req, &fin);
         }
         if (rc != AM_OK) return rc;
         // the scan is the stream's: only now do its teaching replies enter the address gate's map (a scan that was repeated
@@ -1710,16 +1701,16 @@ int am_collect(am_ctx *c, am_packet *out, uint64_t cap, uint64_t *n_out)
         const double TS = am_now_us();
         HIPCHK(c, wait_for_ticket(c, P.seq));
         c->ht[5] += am_now_us() - TS;
-        uint32_t fin = P.req.cur0, M = P.M;
-        int rc = chain_collect(c, P.req, P.M, P.Mp, P.n_max, &fin);
+        uint32_t fin = P.req.cur0;
+        int rc = chain_collect(c, P.req, P.n_max, &fin);
         if (rc == AM_RETRY_EXACT) {
             // more candidates than the capacity the scan was launched for: redo it with the exact count, now
-            rc = run_refine(c, c->ref, &M);
+            rc = run_refine(c, c->scan);
             if (rc == AM_OK) {
                 TailReq req = P.req;
                 req.defer = false;
                 req.gate = c->gate_mode != 0;
-                rc = run_chain_and_slice(c, (const float *)c->bb.p, M, req, &fin);
+                rc = run_chain_and_slice(c, req, &fin);
             }
         }
         if (rc != AM_OK) { P.active = false; P.scanned = false; reset_stream(c); c->multi_off.clear(); c->multi_em.clear(); return rc; }
@@ -1803,9 +1794,9 @@ int am_frontend_work(am_ctx *c, const float *iq, uint64_t n, uint32_t flags, flo
     uint64_t s0 = 0;
     int rc = apply_dcblock(c, &src, &s0, n, 0);
     if (rc != AM_OK) return rc;
-    if (scan_path(c, true) == 2) {
-        uint32_t M = 0;      // (test builds) the tile kernel with an empty detection range: bb/avg only
-        rc = run_front_and_candidates(c, src, 0, n, 0, n, dbb, davg, 0, 0, &M);
+    if (scan_path(c, true) == PATH_TILE) {
+        // (test builds) the tile kernel with an empty detection range: bb/avg only
+        rc = run_front_and_candidates(c, src, 0, n, 0, n, dbb, davg, 0, 0);
     } else {
         rc = run_frontend(c, src, 0, n, 0, n, dbb, davg);
     }
@@ -1841,14 +1832,14 @@ int am_preamble_work(am_ctx *c, const float *in, const float *inavg, uint64_t n,
     c->h_tags.clear();
     c->h_bursts.clear();
     if (flush_limits(c, n, &em)) {
-        uint32_t M = 0, fin = 0;
-        int rc = run_candidates(c, bb, avg, 0, (uint32_t)(em + 1), &M);
+        uint32_t fin = 0;
+        int rc = run_candidates(c, bb, avg, 0, (uint32_t)(em + 1));
         if (rc != AM_OK) return rc;
         TailReq req;
         req.emit_max = (uint32_t)em;
         req.max_hits = (uint32_t)(n / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
         req.keep_bursts = true;
-        rc = run_chain_and_slice(c, bb, M, req, &fin);
+        rc = run_chain_and_slice(c, req, &fin);
         if (rc != AM_OK) return rc;
     }
     return hand_out_tags(c, bursts, tags, cap, n_out);
@@ -1896,8 +1887,8 @@ int am_preamble_stream(am_ctx *c, const float *in, const float *inavg, uint64_t 
         uint64_t emit_max_abs;
         const uint64_t P1 = decidable(c, P0, S1, flush, &emit_max_abs);
         if (P1 > P0) {
-            uint32_t M = 0, fin = 0;
-            int rc = run_candidates(c, bb, avg, (uint32_t)(P0 - A0), (uint32_t)(P1 - A0), &M);
+            uint32_t fin = 0;
+            int rc = run_candidates(c, bb, avg, (uint32_t)(P0 - A0), (uint32_t)(P1 - A0));
             if (rc != AM_OK) return rc;
             TailReq req;
             req.cur0 = c->pb_cur > A0 ? (uint32_t)std::min<uint64_t>(c->pb_cur - A0, 0xFFFFFFF0u) : 0u;
@@ -1905,7 +1896,7 @@ int am_preamble_stream(am_ctx *c, const float *in, const float *inavg, uint64_t 
             req.base_abs = A0;
             req.max_hits = (uint32_t)((P1 - P0) / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
             req.keep_bursts = true;
-            rc = run_chain_and_slice(c, bb, M, req, &fin);
+            rc = run_chain_and_slice(c, req, &fin);
             if (rc != AM_OK) return rc;
             if (A0 + fin > c->pb_cur) c->pb_cur = A0 + fin;
             c->pb_next = P1;
@@ -2103,11 +2094,8 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
     if (fsrc_abs0 > need0) return fail(c, AM_EINVAL, "internal: left halo too short");
     const uint64_t out_n = src_abs1 - out_abs0;
     const uint64_t pad = zero_pad(c->spc_hi);
-    uint32_t M = 0;
-    c->spec_now = false;
-    c->Mdev = nullptr;
     if (P1 > P0 && out_n) {
-        const bool generic = scan_path(c, false) == 1;
+        const bool generic = scan_path(c, false) == PATH_GENERIC;
         ENSURE(c, c->bb, (out_n + pad) * sizeof(float));
         float *bb = (float *)c->bb.p, *avg = nullptr;
         ZERO_TAIL(c, 0, bb, out_n, pad);
@@ -2117,9 +2105,11 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
             ZERO_TAIL(c, 1, avg, out_n, pad);
         }
         int rc = run_front_and_candidates(c, src, fsrc_abs0, src_abs1, out_abs0, out_n, bb, avg,
-                                          (uint32_t)(P0 - out_abs0), (uint32_t)(P1 - out_abs0), &M, true);
+                                          (uint32_t)(P0 - out_abs0), (uint32_t)(P1 - out_abs0), true);
         if (rc != AM_OK) return rc;
-    }
+    } else
+        new_scan(c);                                            // (no position of its own: an empty scan is resident)
+    const Scan &sc = c->scan;
     c->shard_base = out_abs0;
     c->shard_start = abs_start;
     c->shard_end = abs_end;
@@ -2132,8 +2122,8 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
     if (msg_dev) {
         // host-free: the table (what fits the message) and its count go to the device message; whether the capacity
         // this scan was launched for sufficed comes back with the resolve step's completion ticket
-        const uint32_t *Mp = c->spec_now ? c->Mdev : nullptr;
-        int rc = chain_prepare(c, M, true, Mp);
+        const uint32_t M = sc.M, *Mp = sc.Mp;
+        int rc = chain_prepare(c, true);
         if (rc != AM_OK) return rc;
         n_dev = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(M, lead + 1), msg_cap);
         if (int rce = ensure_shard_exit(c); rce != AM_OK) return rce;
@@ -2150,8 +2140,8 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
         return AM_OK;
     }
     for (int attempt = 0; attempt < 2; ++attempt) {
-        const uint32_t *Mp = c->spec_now ? c->Mdev : nullptr;
-        int rc = chain_prepare(c, M, true, Mp);
+        const uint32_t M = sc.M, *Mp = sc.Mp;
+        int rc = chain_prepare(c, true);
         if (rc != AM_OK) return rc;
         n_dev = (uint32_t)std::min<uint64_t>(M, lead + 1);
         uint32_t actual = M;
@@ -2183,7 +2173,7 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
 #if defined(AM_TEST_KNOBS)
         if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: shard capacity %u < %u candidates, scan redone\n", M, actual);
 #endif
-        rc = run_refine(c, c->ref, &M);
+        rc = run_refine(c, c->scan);
         if (rc != AM_OK) return rc;
     }
     note_density(c, P1 - P0);
@@ -2319,7 +2309,7 @@ int am_shard_resolve(am_ctx *c, uint64_t cur_in, am_packet *out, uint64_t cap, u
     }
     req.cur0 = cur_in > c->shard_base ? (uint32_t)std::min<uint64_t>(cur_in - c->shard_base, 0xFFFFFFF0u) : 0u;
     uint32_t fin = 0;
-    int rc = chain_finish(c, (const float *)c->bb.p, req, &fin);
+    int rc = chain_finish(c, req, &fin);
     if (rc != AM_OK) return rc;
     c->last_tags = c->n_hits;
     return hand_out(c, out, cap, n_out);
@@ -2356,7 +2346,7 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
         return AM_OK;
     }
     uint32_t fin = 0;
-    int rc = chain_finish(c, (const float *)c->bb.p, req, &fin);
+    int rc = chain_finish(c, req, &fin);
     // the dominant kernel's event pair of this step's scan (am_shard_scan_async only enqueued): both events lie in front of
     // the completion ticket chain_finish waited for -- also where the scan outgrew its capacity
     if (rc != AM_OK && rc != AM_RETRY_EXACT) { c->last_dom_ms = 0.0f; return rc; }
@@ -2459,9 +2449,9 @@ static int shard_resolve_enqueue(am_ctx *c, const am_shard_exit *msgs, uint32_t 
     req.walk_event = walk_done;
     req.defer = true;
     uint32_t fin = 0;
-    int rc = chain_finish(c, (const float *)c->bb.p, req, &fin);
+    int rc = chain_finish(c, req, &fin);
     if (rc != AM_DEFERRED) return rc == AM_OK ? fail(c, AM_EHIP, "internal: the resolve step was not deferred") : rc;
-    P.active = true;                                            // (chain_finish filled in scanned / seq / M / Mp / n_max / req)
+    P.active = true;                                            // (chain_finish filled in scanned / seq / n_max / req)
     return AM_OK;
 }
 
@@ -2477,7 +2467,7 @@ static int shard_resolve_complete(am_ctx *c, int *redo, uint64_t *exit_after)
     int rc = AM_OK;
     if (P.scanned) {
         uint32_t fin = 0;
-        rc = chain_collect(c, P.req, P.M, P.Mp, P.n_max, &fin);
+        rc = chain_collect(c, P.req, P.n_max, &fin);
         if (rc == AM_RETRY_EXACT) { *redo = 1; rc = AM_OK; }
     } else
         c->tail_synced = true;
@@ -2916,7 +2906,7 @@ int am_last_timing(am_ctx *c, float *total_ms, float *dom_ms)
     return AM_OK;
 }
 
-int am_last_frontend(const am_ctx *c) { return c ? c->last_fe : AM_EINVAL; }
+int am_last_frontend(const am_ctx *c) { return c ? (int)c->scan.path : AM_EINVAL; }
 
 long long am_last_num_candidates(const am_ctx *c)
 {

@@ -691,66 +691,27 @@ __global__ void __launch_bounds__(FE3_NT, FE3_WPS) am_k_fe3(am_fe3_args a)
 }
 
 // ---- host side ----------------------------------------------------------------------------------------
-unsigned am_fe3_tile(void) { return FE3_T; }
-unsigned am_fe3_lag(void) { return FE3_LAG * FE3_SPC; }
 unsigned am_fe3_waves(void) { return FE3_NW; }
-unsigned am_fe3_steps(long long out_n) { return (unsigned)((out_n + FE3_LAG * FE3_SPC + FE3_T - 1) / FE3_T); }
 
-
-static int fe3_wgs_for_device() { return FE3_WG_PER_CU * am_device_cus(); }   // resident workgroups
-
-hipError_t am_launch_fe3(const float *iq, long long src_abs0, long long src_abs1, long long out_abs0, long long out_n,
-                         float *bb_sparse, float *avg_sparse, uint32_t j0, uint32_t j1, int use_pmf, float s1, float sL,
-                         float thr_lin, uint32_t *bits, uint32_t *wg_cnt, float *wg_max, unsigned *nsteps, unsigned *steps_per_wg,
-                         hipStream_t s, int wgs_per_cu, unsigned *n_long)
+hipError_t am_launch_fe3(const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu, bool levelled)
 {
-    am_fe3_args a;
-    a.iq = iq; a.src_abs0 = src_abs0; a.src_abs1 = src_abs1; a.out_abs0 = out_abs0; a.out_n = out_n;
-    a.bb_sparse = bb_sparse; a.avg_sparse = avg_sparse; a.j0 = j0; a.j1 = j1; a.bits = bits; a.wg_cnt = wg_cnt; a.wg_max = wg_max;
-    a.use_pmf = (use_pmf && FE3_SPC > 1) ? 1 : 0; a.s1 = s1; a.sL = sL; a.thr_lin = thr_lin;
-    a.nsteps = am_fe3_steps(out_n);
-    *nsteps = a.nsteps;
-    *steps_per_wg = 1;
-    if (a.nsteps == 0) return hipSuccess;
-    // steps served by DMA: samples [out_abs0 + k T, + T) inside [src_abs0, src_abs1), source 16-byte aligned (the
-    // parity of the offset is the same for every step: T is even)
-    const bool aligned = ((reinterpret_cast<uintptr_t>(iq) + (uintptr_t)(out_abs0 - src_abs0) * 8u) & 15u) == 0;
-    auto clampi = [](long long v) { return (int)(v < -4 ? -4 : (v > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : v)); };
-    a.raw_lo = clampi(fes_ceil_div(src_abs0 - out_abs0, FE3_T));
-    a.raw_hi = aligned ? clampi(fes_floor_div(src_abs1 - out_abs0, FE3_T)) : a.raw_lo;
-    // steps whose tested positions [k T - 288, k T + T - 288) all lie in [j0, min(j1, out_n))
-    const long long lag = (long long)FE3_LAG * FE3_SPC;
-    const long long jhi = (long long)j1 < out_n ? (long long)j1 : out_n;
-    a.test_lo = clampi(fes_ceil_div((long long)j0 + lag, FE3_T));
-    a.test_hi = clampi(fes_floor_div(jhi + lag, FE3_T));
-    // persistent workgroups: as many as are resident at once, each with a contiguous run of steps; short inputs
-    // get at least 4 steps per workgroup (the ring rebuild costs one)
-    unsigned resident = (unsigned)fe3_wgs_for_device();
+    // persistent workgroups: as many as are resident at once, each with a contiguous run of steps (am_fe_plan)
+    unsigned resident = (unsigned)(FE3_WG_PER_CU * am_device_cus());
     if (wgs_per_cu > 0 && wgs_per_cu < FE3_WG_PER_CU) resident = (unsigned)(wgs_per_cu * am_device_cus());   // (am_pipe: room for other batches' tails)
 #if defined(AM_TEST_KNOBS)
     if (const char *e = getenv("AIRMODES_FE3_WGS_PER_CU"))            // tuning: leave room on every CU for another batch's tail
         if (atoi(e) > 0) resident = (unsigned)(atoi(e) * am_device_cus());
 #endif
-    unsigned spw = (a.nsteps + resident - 1) / resident;
-    if (spw < 4) spw = 4;
-#ifdef FE3_FORCE_SPW
-    spw = FE3_FORCE_SPW;                                              // tuning builds
+#ifndef FE3_FORCE_SPW
+#define FE3_FORCE_SPW 0                                               /* tuning builds: steps per workgroup */
 #endif
-    unsigned grid = (a.nsteps + spw - 1) / spw;
-    a.n_long = grid;
-    if (n_long) {
-        // the caller can place segments of two lengths (am_k_refine_seg): as many workgroups as are resident (at least ~4 steps each),
-        // the steps dealt out as evenly as they go
-        unsigned G = a.nsteps / 4u;
-        G = G < 1u ? 1u : (G > resident ? resident : G);
-        const unsigned lo = a.nsteps / G, r = a.nsteps - lo * G;
-        grid = G;
-        if (r == 0) { spw = lo; a.n_long = G; }
-        else { spw = lo + 1u; a.n_long = r; }
-        *n_long = a.n_long;
-    }
-    a.steps_per_wg = spw;
-    *steps_per_wg = spw;
+    const am_fe_layout l = *layout = am_fe_plan(FE3_SPC, r.out_n, resident, levelled, FE3_FORCE_SPW);
+    if (l.tile != FE3_T || l.lag != FE3_LAG * FE3_SPC || l.wps != FE3_NW * AM_CHIPS_AVG) return hipErrorInvalidValue;   // (not this kernel's bitmap)
+    if (l.nsteps == 0) return hipSuccess;
+    am_fe3_args a;
+    fes_fill_args(a, r, l);
+    a.n_long = l.n_long;
+    const unsigned grid = l.nwg;
     static std::atomic<bool> attr_done[64];
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -760,7 +721,6 @@ hipError_t am_launch_fe3(const float *iq, long long src_abs0, long long src_abs1
         if (rc != hipSuccess) return rc;
         if (dev >= 0 && dev < 64) attr_done[dev].store(true, std::memory_order_release);
     }
-    a.prof = nullptr;
 #if defined(FE3_PROFILE)
     // blocking; prints mean cycles per step and phase (wave 0 / wave 1) -- never in the default build
     if (hipMalloc(reinterpret_cast<void **>(&a.prof), (size_t)grid * FE3_NW * 12 * sizeof(long long)) != hipSuccess) a.prof = nullptr;
@@ -771,7 +731,7 @@ hipError_t am_launch_fe3(const float *iq, long long src_abs0, long long src_abs1
     if (a.prof) {
         int occ = 0;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(&am_k_fe3), FE3_NT, FE3_LDS_BYTES);
-        fprintf(stderr, "fe3: grid %u, %u steps per workgroup, %d bytes of LDS, runtime says %d workgroups per CU\n", grid, spw,
+        fprintf(stderr, "fe3: grid %u, %u steps per workgroup, %d bytes of LDS, runtime says %d workgroups per CU\n", grid, l.spw,
                 (int)FE3_LDS_BYTES, occ);
         std::vector<long long> h((size_t)grid * FE3_NW * 12);
         (void)hipStreamSynchronize(s);
@@ -783,7 +743,7 @@ hipError_t am_launch_fe3(const float *iq, long long src_abs0, long long src_abs1
             double acc[12] = {};
             for (unsigned b = 0; b < grid; ++b)
                 for (int k = 0; k < 12; ++k) acc[k] += (double)h[((size_t)b * FE3_NW + w) * 12 + k];
-            const double steps = (double)grid * (double)(spw + 1);
+            const double steps = (double)grid * (double)(l.spw + 1);
             double tot = 0;
             for (int k = 0; k < 7; ++k) tot += acc[k];
             fprintf(stderr, "fe3 clocks/step wave %d (total %.0f):", w, tot / steps);
@@ -810,7 +770,7 @@ hipError_t am_launch_fe3(const float *iq, long long src_abs0, long long src_abs1
             };
             pct(t0, "start"); pct(t1, "rings rebuilt"); pct(t2, "first tested step done"); pct(t3, "end");
             std::vector<double> dur(grid), per(grid);
-            for (unsigned b = 0; b < grid; ++b) { dur[b] = t3[b] - t0[b]; per[b] = (t3[b] - t2[b]) / (double)(spw > 1 ? spw - 1 : 1); }
+            for (unsigned b = 0; b < grid; ++b) { dur[b] = t3[b] - t0[b]; per[b] = (t3[b] - t2[b]) / (double)(l.spw > 1 ? l.spw - 1 : 1); }
             pct(dur, "duration");
             pct(per, "per step after the 1st");
             // by CU: do a CU's workgroups end together (the chip drains CU by CU) or one after the other (every CU is busy to the end)?

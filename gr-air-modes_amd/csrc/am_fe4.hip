@@ -874,8 +874,33 @@ unsigned am_fe4_steps(long long out_n, int spc)
     return T ? (unsigned)((out_n + am_fe4_lag(spc) + T - 1) / T) : 0u;
 }
 
+// The one place the bitmap's layout is decided (am_internal.h: am_fe_layout).
+am_fe_layout am_fe_plan(int spc, long long out_n, unsigned resident, bool levelled, unsigned force_spw)
+{
+    am_fe_layout l;
+    l.wbits = am_fe4_unit(spc); l.lag = am_fe4_lag(spc); l.wps = am_fe4_words(spc) * am_fe4_waves(spc); l.tile = am_fe4_tile(spc);
+    l.nsteps = am_fe4_steps(out_n, spc);
+    if (l.nsteps == 0) return l;
+    if (resident < 1u) resident = 1u;
+    if (levelled && FE4_USE_FE3(spc)) {
+        // as many workgroups as are resident (at least ~4 steps each), the steps dealt out as evenly as they go
+        const unsigned quarter = l.nsteps / 4u;
+        l.nwg = quarter < 1u ? 1u : (quarter > resident ? resident : quarter);
+        const unsigned lo = l.nsteps / l.nwg, r = l.nsteps - lo * l.nwg;
+        l.spw = r ? lo + 1u : lo;
+        l.n_long = r ? r : l.nwg;
+        return l;
+    }
+    // short inputs get at least 4 steps per workgroup (the ring rebuild costs one)
+    l.spw = (l.nsteps + resident - 1) / resident;
+    if (l.spw < 4) l.spw = 4;
+    if (force_spw) l.spw = force_spw;
+    l.nwg = l.n_long = (l.nsteps + l.spw - 1) / l.spw;
+    return l;
+}
+
 template <int SPC, int G, int NW>
-static hipError_t fe4_launch(am_fe4_args &a, unsigned *steps_per_wg, hipStream_t s, int wgs_per_cu)
+static hipError_t fe4_launch(const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu)
 {
     using C = fe4_cfg<SPC, G, NW>;
     const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
@@ -901,16 +926,14 @@ static hipError_t fe4_launch(am_fe4_args &a, unsigned *steps_per_wg, hipStream_t
         if (atoi(e) > 0) wpc = atoi(e);
 #endif
     if (wgs_per_cu > 0 && wgs_per_cu < wpc) wpc = wgs_per_cu;         // (am_pipe: room on every CU for other batches' tails, as am_launch_fe3)
-    const unsigned resident = (unsigned)(wpc * am_device_cus());
-    unsigned spw = (a.nsteps + resident - 1) / resident;
-    if (spw < 4) spw = 4;
-#ifdef FE4_FORCE_SPW
-    spw = FE4_FORCE_SPW;                                              // tuning builds
+#ifndef FE4_FORCE_SPW
+#define FE4_FORCE_SPW 0                                               /* tuning builds: steps per workgroup */
 #endif
-    a.steps_per_wg = spw;
-    *steps_per_wg = spw;
-    const unsigned grid = (a.nsteps + spw - 1) / spw;
-    a.prof = nullptr;
+    // (am_k_fe4 places one segment length: never levelled)
+    const am_fe_layout l = *layout = am_fe_plan(SPC, r.out_n, (unsigned)(wpc * am_device_cus()), false, FE4_FORCE_SPW);
+    am_fe4_args a;
+    fes_fill_args(a, r, l);
+    const unsigned grid = l.nwg;
 #if defined(FE4_PROFILE)
     // blocking; prints mean cycles per step and phase -- never in the default build
     if (hipMalloc(reinterpret_cast<void **>(&a.prof), (size_t)grid * NW * 8 * sizeof(long long)) != hipSuccess) a.prof = nullptr;
@@ -919,7 +942,7 @@ static hipError_t fe4_launch(am_fe4_args &a, unsigned *steps_per_wg, hipStream_t
     hipError_t lrc = hipGetLastError();
 #if defined(FE4_PROFILE)
     if (a.prof) {
-        fprintf(stderr, "fe4<%d,%d,%d>: grid %u, %u steps per workgroup, %d bytes of LDS, %d workgroups per CU\n", SPC, G, NW, grid, spw,
+        fprintf(stderr, "fe4<%d,%d,%d>: grid %u, %u steps per workgroup, %d bytes of LDS, %d workgroups per CU\n", SPC, G, NW, grid, l.spw,
                 (int)lds, wpc);
         std::vector<long long> h((size_t)grid * NW * 8);
         (void)hipStreamSynchronize(s);
@@ -931,7 +954,7 @@ static hipError_t fe4_launch(am_fe4_args &a, unsigned *steps_per_wg, hipStream_t
             double acc[8] = {};
             for (unsigned b = 0; b < grid; ++b)
                 for (int k = 0; k < 8; ++k) acc[k] += (double)h[((size_t)b * NW + w) * 8 + k];
-            const double steps = (double)grid * (double)(spw + 1);
+            const double steps = (double)grid * (double)(l.spw + 1);
             double tot = 0;
             for (int k = 0; k < 7; ++k) tot += acc[k];
             fprintf(stderr, "fe4 clocks/step wave %d (total %.0f):", w, tot / steps);
@@ -944,46 +967,22 @@ static hipError_t fe4_launch(am_fe4_args &a, unsigned *steps_per_wg, hipStream_t
     return lrc;
 }
 
-hipError_t am_launch_fe4(int spc, const float *iq, long long src_abs0, long long src_abs1, long long out_abs0, long long out_n,
-                         float *bb_sparse, float *avg_sparse, uint32_t j0, uint32_t j1, int use_pmf, float s1, float sL,
-                         float thr_lin, uint32_t *bits, uint32_t *wg_cnt, float *wg_max, unsigned *nsteps,
-                         unsigned *steps_per_wg, hipStream_t s, int wgs_per_cu, unsigned *n_long)
+hipError_t am_launch_fe4(int spc, const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu, bool levelled)
 {
     if (!am_fe4_supported(spc)) return hipErrorInvalidValue;
-    if (FE4_USE_FE3(spc))
-        return am_launch_fe3(iq, src_abs0, src_abs1, out_abs0, out_n, bb_sparse, avg_sparse, j0, j1, use_pmf, s1, sL, thr_lin, bits,
-                             wg_cnt, wg_max, nsteps, steps_per_wg, s, wgs_per_cu, n_long);
-    am_fe4_args a;
-    a.iq = iq; a.src_abs0 = src_abs0; a.src_abs1 = src_abs1; a.out_abs0 = out_abs0; a.out_n = out_n;
-    a.bb_sparse = bb_sparse; a.avg_sparse = avg_sparse; a.j0 = j0; a.j1 = j1; a.bits = bits; a.wg_cnt = wg_cnt; a.wg_max = wg_max;
-    a.use_pmf = use_pmf ? 1 : 0; a.s1 = s1; a.sL = sL; a.thr_lin = thr_lin;
-    a.nsteps = am_fe4_steps(out_n, spc);
-    a.prof = nullptr;
-    *nsteps = a.nsteps;
-    *steps_per_wg = 1;
-    if (a.nsteps == 0) return hipSuccess;
-    const long long T = am_fe4_tile(spc), lag = am_fe4_lag(spc);
-    // steps loaded without guards: samples [out_abs0 + k T, + T) inside [src_abs0, src_abs1), source 16-byte aligned (the
-    // parity of the offset is the same for every step: T is even)
-    const bool aligned = ((reinterpret_cast<uintptr_t>(iq) + (uintptr_t)(out_abs0 - src_abs0) * 8u) & 15u) == 0 && (T % 2) == 0;
-    auto clampi = [](long long v) { return (int)(v < -4 ? -4 : (v > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : v)); };
-    a.raw_lo = clampi(fes_ceil_div(src_abs0 - out_abs0, T));
-    a.raw_hi = aligned ? clampi(fes_floor_div(src_abs1 - out_abs0, T)) : a.raw_lo;
-    // steps whose tested positions [k T - lag, k T + T - lag) all lie in [j0, min(j1, out_n))
-    const long long jhi = (long long)j1 < out_n ? (long long)j1 : out_n;
-    a.test_lo = clampi(fes_ceil_div((long long)j0 + lag, T));
-    a.test_hi = clampi(fes_floor_div(jhi + lag, T));
+    if (FE4_USE_FE3(spc)) return am_launch_fe3(r, layout, s, wgs_per_cu, levelled);
+    if (am_fe4_steps(r.out_n, spc) == 0) { *layout = am_fe_plan(spc, r.out_n, 1, false); return hipSuccess; }   // nothing to launch
     switch (spc) {
-    case 1: return fe4_launch<1, 24, 2>(a, steps_per_wg, s, wgs_per_cu);
-    case 2: return fe4_launch<2, 16, 2>(a, steps_per_wg, s, wgs_per_cu);
-    case 4: return fe4_launch<4, 8, 2>(a, steps_per_wg, s, wgs_per_cu);
-    case 5: return fe4_launch<5, 6, 2>(a, steps_per_wg, s, wgs_per_cu);
-    case 8: return fe4_launch<8, 4, 2>(a, steps_per_wg, s, wgs_per_cu);
-    case 10: return fe4_launch<10, 3, 2>(a, steps_per_wg, s, wgs_per_cu);
-    case 16: return fe4_launch<16, 2, 2>(a, steps_per_wg, s, wgs_per_cu);
-    case 20: return fe4_launch<20, 1, 2>(a, steps_per_wg, s, wgs_per_cu);
+    case 1: return fe4_launch<1, 24, 2>(r, layout, s, wgs_per_cu);
+    case 2: return fe4_launch<2, 16, 2>(r, layout, s, wgs_per_cu);
+    case 4: return fe4_launch<4, 8, 2>(r, layout, s, wgs_per_cu);
+    case 5: return fe4_launch<5, 6, 2>(r, layout, s, wgs_per_cu);
+    case 8: return fe4_launch<8, 4, 2>(r, layout, s, wgs_per_cu);
+    case 10: return fe4_launch<10, 3, 2>(r, layout, s, wgs_per_cu);
+    case 16: return fe4_launch<16, 2, 2>(r, layout, s, wgs_per_cu);
+    case 20: return fe4_launch<20, 1, 2>(r, layout, s, wgs_per_cu);
 #if defined(FE4_64MSPS)
-    default: return fe4_launch<32, 1, FE4_NW64>(a, steps_per_wg, s, wgs_per_cu);
+    default: return fe4_launch<32, 1, FE4_NW64>(r, layout, s, wgs_per_cu);
 #else
     default: return hipErrorInvalidValue;
 #endif

@@ -172,4 +172,28 @@ __device__ __forceinline__ void fes_step_priority(unsigned k)
 static inline long long fes_floor_div(long long x, long long d) { return x >= 0 ? x / d : -((-x + d - 1) / d); }
 static inline long long fes_ceil_div(long long x, long long d) { return -fes_floor_div(-x, d); }
 
+// Host side: the kernel arguments am_k_fe3 and am_k_fe4 have in common (am_fe3_args / am_fe4_args: the same fields under the
+// same names), from the request and the layout the launch was planned with.
+template <class A>
+static inline void fes_fill_args(A &a, const am_fe_stream_req &r, const am_fe_layout &l)
+{
+    a.iq = r.iq; a.src_abs0 = r.src_abs0; a.src_abs1 = r.src_abs1; a.out_abs0 = r.out_abs0; a.out_n = r.out_n;
+    a.bb_sparse = r.bb_sparse; a.avg_sparse = r.avg_sparse; a.j0 = r.j0; a.j1 = r.j1;
+    a.bits = r.bits; a.wg_cnt = r.wg_cnt; a.wg_max = r.wg_max;
+    a.use_pmf = r.use_pmf ? 1 : 0; a.s1 = r.s1; a.sL = r.sL; a.thr_lin = r.thr_lin;
+    a.nsteps = l.nsteps; a.steps_per_wg = l.spw;
+    a.prof = nullptr;
+    const long long T = l.tile, lag = l.lag;
+    // steps loaded without guards: samples [out_abs0 + k T, + T) inside [src_abs0, src_abs1), source 16-byte aligned (the parity
+    // of the offset is the same for every step when T is even: am_k_fe3's 3072 is)
+    const bool aligned = ((reinterpret_cast<uintptr_t>(r.iq) + (uintptr_t)(r.out_abs0 - r.src_abs0) * 8u) & 15u) == 0 && (T % 2) == 0;
+    auto clampi = [](long long v) { return (int)(v < -4 ? -4 : (v > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : v)); };
+    a.raw_lo = clampi(fes_ceil_div(r.src_abs0 - r.out_abs0, T));
+    a.raw_hi = aligned ? clampi(fes_floor_div(r.src_abs1 - r.out_abs0, T)) : a.raw_lo;
+    // steps whose tested positions [k T - lag, k T + T - lag) all lie in [j0, min(j1, out_n)): no range mask
+    const long long jhi = (long long)r.j1 < r.out_n ? (long long)r.j1 : r.out_n;
+    a.test_lo = clampi(fes_ceil_div((long long)r.j0 + lag, T));
+    a.test_hi = clampi(fes_floor_div(jhi + lag, T));
+}
+
 #endif

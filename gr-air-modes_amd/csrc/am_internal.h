@@ -1,5 +1,6 @@
-// am_internal.h -- kernel launch interface between am_capi.hip (host logic) and
-// am_kernels.hip (gfx950 kernels).  Not part of the public ABI.
+// am_internal.h -- kernel launch interface between am_capi.hip (host logic) and the gfx950 kernels with their launchers:
+// am_kernels.hip, am_fe2.hip (test builds), am_fe3.hip, am_fe4.hip, am_refine_seg.hip, am_dcblock.hip, am_resample.hip.
+// Not part of the public ABI.
 #ifndef AM_INTERNAL_H
 #define AM_INTERNAL_H
 
@@ -63,37 +64,63 @@ hipError_t am_launch_fe2(int spc, const float *iq, long long src_abs0, long long
                          long long out_n, float *bb, float *avg, uint32_t j0, uint32_t j1, int use_pmf, float s1,
                          float sL, float thr_lin, uint32_t *seg_pos, float *avg_sparse, uint32_t *blk_cnt,
                          unsigned *ntiles, unsigned *tile_len, hipStream_t s);
-/* streaming fused front ends (am_fe4.hip; am_fe3.hip at 64 Msps): persistent workgroups, LDS rings, sparse outputs.  A lane takes a unit of G chips
- * = am_fe4_unit(spc) samples (one 32-sample chip at 64 Msps).  Candidates leave as a bitmap, a word per unit: bit b of word w =
- * array coordinate w * am_fe4_unit(spc) + b - am_fe4_lag(spc); a step has am_fe4_waves(spc) x am_fe4_words(spc) words (waves of 64
- * words at 20, 10 and 2 Msps, of 48 otherwise).  wg_cnt[g] = candidates workgroup g found; wg_max[g] (nsteps + 8
- * floats are enough) = the largest bb workgroup g formed, +inf if one was not finite; workgroup g formed the bb of the array
- * coordinates [g * steps_per_wg * tile, (g + 1) * steps_per_wg * tile) (and some before them). */
-/* (behind am_fe4_* / am_launch_fe4 at 64 Msps: am_k_fe3, am_fe3.hip -- the same machine with one 32-sample chip per lane and
- * 16-byte LDS rows; two segments of 48 words per step, lag 288) */
-unsigned am_fe3_tile(void);                 /* positions per step (3072) */
-unsigned am_fe3_lag(void);                  /* 288 */
-unsigned am_fe3_waves(void);                /* segments (waves, 48 chips = 48 bitmap words each) per step */
-unsigned am_fe3_steps(long long out_n);
-hipError_t am_launch_fe3(const float *iq, long long src_abs0, long long src_abs1, long long out_abs0, long long out_n,
-                         float *bb_sparse, float *avg_sparse, uint32_t j0, uint32_t j1, int use_pmf, float s1, float sL,
-                         float thr_lin, uint32_t *bits, uint32_t *wg_cnt, float *wg_max, unsigned *nsteps,
-                         unsigned *steps_per_wg, hipStream_t s, int wgs_per_cu, unsigned *n_long = nullptr);
-/* (n_long != null: LEVELLED segments -- the first *n_long workgroups take *steps_per_wg steps, the others one fewer, the grid is as
- * many workgroups as are resident; only a caller whose later kernels can place two segment lengths asks for it: am_k_refine_seg) */
+/* ---- streaming fused front ends (am_fe4.hip; am_fe3.hip at 64 Msps) and what reads their bitmap -------------------------------
+ * Persistent workgroups, LDS rings, sparse outputs.  A lane takes a unit of G chips = am_fe4_unit(spc) samples (one 32-sample
+ * chip at 64 Msps).  Candidates leave as a bitmap, a word per unit; a step has am_fe4_waves(spc) x am_fe4_words(spc) words
+ * (waves of 64 words at 20, 10 and 2 Msps, of 48 otherwise).  wg_cnt[g] = candidates workgroup g found; wg_max[g] (nsteps + 8
+ * floats are enough) = the largest bb workgroup g formed, +inf if one was not finite.
+ * (64 Msps: am_k_fe3 -- one 32-sample chip per lane, 16-byte LDS rows, two segments of 48 words per step, lag 288) */
 int am_fe4_supported(int spc);
-unsigned am_fe4_unit(int spc);
-unsigned am_fe4_words(int spc);
-unsigned am_fe4_waves(int spc);
-unsigned am_fe4_tile(int spc);
+unsigned am_fe4_unit(int spc);              /* positions per bitmap word                                        */
+unsigned am_fe4_words(int spc);             /* bitmap words per step and wave                                   */
+unsigned am_fe4_waves(int spc);             /* segments (waves) per step                                        */
+unsigned am_fe4_tile(int spc);              /* positions per step                                               */
 unsigned am_fe4_lag(int spc);
 unsigned am_fe4_steps(long long out_n, int spc);
-hipError_t am_launch_fe4(int spc, const float *iq, long long src_abs0, long long src_abs1, long long out_abs0, long long out_n,
-                         float *bb_sparse, float *avg_sparse, uint32_t j0, uint32_t j1, int use_pmf, float s1, float sL,
-                         float thr_lin, uint32_t *bits, uint32_t *wg_cnt, float *wg_max, unsigned *nsteps,
-                         unsigned *steps_per_wg, hipStream_t s, int wgs_per_cu, unsigned *n_long = nullptr);
-/* (wgs_per_cu: 0 = as many persistent workgroups as are resident at once; n > 0 = at most n per CU -- am_pipe leaves room on
- * every CU for the small kernels of the other batches in flight; honoured by am_k_fe3) */
+unsigned am_fe3_waves(void);                /* am_k_fe3's segments (48 chips = 48 bitmap words each) per step   */
+
+/* The bitmap a streaming front end leaves and who made which part of it: workgroup g took a contiguous run of steps and formed
+ * the bb of their array coordinates (and some before them).  Computed ONCE, by am_fe_plan: the front-end launchers launch from
+ * it, everything behind them reads it. */
+struct am_fe_layout {
+    uint32_t wbits = 32;      /* positions per bitmap word                                                       */
+    uint32_t lag = 0;         /* bit b of word w = array coordinate w * wbits + b - lag                          */
+    uint32_t wps = 0;         /* bitmap words per step                                                           */
+    uint32_t tile = 0;        /* positions per step (= wps * wbits)                                              */
+    uint32_t nsteps = 0;
+    uint32_t nwg = 0;         /* workgroups (the front end's grid)                                               */
+    uint32_t spw = 1;         /* steps per workgroup (of the long ones)                                          */
+    uint32_t n_long = 0;      /* LEVELLED segments: the first n_long workgroups take spw steps, the others spw - 1 */
+    bool alike() const { return n_long >= nwg; }               /* n_long == nwg: one segment length                   */
+    uint32_t steps_short() const { return alike() ? spw : spw - 1u; }
+    uint32_t words_per_wg() const { return spw * wps; }
+    uint32_t words_short() const { return steps_short() * wps; }
+    uint32_t nwords() const { return nsteps * wps; }
+    uint32_t vspan() const { return spw * tile; }              /* array coordinates per workgroup: wg_max[coordinate / vspan] */
+    uint32_t vspan_short() const { return steps_short() * tile; }
+    uint32_t nv() const { return nwg; }                        /* entries of wg_cnt / wg_max                          */
+};
+/* Pure arithmetic.  resident: workgroups that run at once -- the launchers' business (occupancy, wgs_per_cu, test knobs).
+ * Unlevelled: ceil(nsteps / resident) steps per workgroup, at least 4, or force_spw (tuning builds).  levelled (honoured where
+ * am_k_fe3 runs; asked for by the caller whose later kernel places two segment lengths too: am_k_refine_seg): min(resident,
+ * nsteps / 4) workgroups, the steps dealt out as evenly as they go. */
+am_fe_layout am_fe_plan(int spc, long long out_n, unsigned resident, bool levelled, unsigned force_spw = 0);
+
+/* what a streaming front end is launched for (the fields am_fe3_args / am_fe4_args describe) */
+struct am_fe_stream_req {
+    const float *iq;
+    long long src_abs0, src_abs1, out_abs0, out_n;
+    float *bb_sparse, *avg_sparse;        /* (bb_sparse null: am_k_fe3 writes no rows)                       */
+    uint32_t j0, j1;
+    int use_pmf;
+    float s1, sL, thr_lin;
+    uint32_t *bits, *wg_cnt;
+    float *wg_max;
+};
+/* *layout: what was launched (nsteps == 0: nothing).  wgs_per_cu: 0 = as many persistent workgroups as are resident at once;
+ * n > 0 = at most n per CU -- am_pipe leaves room on every CU for the small kernels of the other batches in flight. */
+hipError_t am_launch_fe3(const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu, bool levelled);
+hipError_t am_launch_fe4(int spc, const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu, bool levelled);
 /* flat candidate positions from the bitmap, one workgroup per front-end workgroup: workgroup g owns the words
  * [g * words_per_wg, (g + 1) * words_per_wg) (nwords in all) and starts its part of pos[] at the sum of wg_cnt[0 .. g)
  * -- no scan launch, no chain.  Entries at or beyond Mcap are dropped; *total_out = the number of candidates. */
@@ -110,15 +137,13 @@ struct am_rows_args {
     int use_pmf;
     float s1;
 };
-hipError_t am_launch_gather_wg(const uint32_t *bits, const uint32_t *wg_cnt, uint32_t nwg, uint32_t words_per_wg,
-                               uint32_t nwords, uint32_t Mcap, uint32_t lag, uint32_t wbits, uint32_t *pos,
+hipError_t am_launch_gather_wg(const uint32_t *bits, const uint32_t *wg_cnt, const am_fe_layout &l, uint32_t Mcap, uint32_t *pos,
                                uint32_t *total_out, hipStream_t s, const am_rows_args *rows = nullptr);
 /* 64 Msps (round 6): candidate list + bb rows + refinement in ONE launch, one workgroup per front-end workgroup, the rows in LDS
  * (am_refine_seg.hip): what am_launch_gather_wg(rows) + am_launch_refine_late(bb_max) leave in pos / e / tgt / inavg / valid / jump0,
- * bit for bit, without the bb rows ever reaching memory.  rows: the samples (bb_sparse / bb_max are not used).  Segments: the first
- * n_long front-end workgroups tested words_per_wg words each, the others words_per_wg - words_per_step (levelled: am_launch_fe3) */
-hipError_t am_launch_refine_seg(const uint32_t *bits, const uint32_t *wg_cnt, const float *wg_max, uint32_t nwg, uint32_t n_long,
-                                uint32_t words_per_wg, uint32_t words_per_step, uint32_t nwords, uint32_t Mcap, uint32_t lag, uint32_t wbits, uint32_t vspan, uint32_t nv,
+ * bit for bit, without the bb rows ever reaching memory.  rows: the samples (bb_sparse / bb_max are not used).  Places the
+ * layout's two segment lengths. */
+hipError_t am_launch_refine_seg(const uint32_t *bits, const uint32_t *wg_cnt, const float *wg_max, const am_fe_layout &l, uint32_t Mcap,
                                 const am_rows_args &rows, const float *avg_sparse, float thr_lin, uint32_t end_j, uint32_t *pos,
                                 uint32_t *e, uint32_t *tgt, float *inavg, uint8_t *valid, uint32_t *jump0, uint32_t *total_out,
                                 hipStream_t s);
@@ -135,11 +160,11 @@ hipError_t am_launch_cand(const float *bb, const float *avg_sparse, const uint32
                           int spc, float thr_lin, uint32_t end_j, uint32_t *e, uint32_t *tgt, float *inavg,
                           uint8_t *valid, uint32_t *jump0, hipStream_t s, const uint32_t *Mp = nullptr);
 /* behind the streaming front ends: late-peak decisions + per-candidate test + record + successor in one launch (the
- * decisions stay in LDS; no dcount / compact offsets).  vmax[array coordinate / vspan] (nv entries) bounds the samples */
+ * decisions stay in LDS; no dcount / compact offsets).  vmax[array coordinate / l.vspan()] (l.nv() entries) bounds the samples */
 hipError_t am_launch_refine_late(const float *bb, const float *avg_sparse, const uint32_t *pos, uint32_t M, int spc,
                                  float thr_lin, uint32_t end_j, uint32_t *e, uint32_t *tgt, float *inavg, uint8_t *valid,
-                                 uint32_t *jump0, hipStream_t s, const uint32_t *Mp, const float *vmax, uint32_t vspan,
-                                 uint32_t nv, const float *bb_max = nullptr);
+                                 uint32_t *jump0, hipStream_t s, const uint32_t *Mp, const float *vmax, const am_fe_layout &l,
+                                 const float *bb_max = nullptr);
 /* (bb_max, 32 samples per chip only: bb_max[c] = the largest bb of array chip c for every chip whose row exists -- am_k_gather_wg<1>
  * writes it with the rows; a quiet zone's whole chips are then judged by six numbers instead of 192 samples) */
 /* exclusive scan of n counts in ONE launch (2048 per workgroup, chained through slots[]: am_chain_prefix);

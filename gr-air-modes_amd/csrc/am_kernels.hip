@@ -862,12 +862,12 @@ am_k_gather_wg(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ w
     }
 }
 
-hipError_t am_launch_gather_wg(const uint32_t *bits, const uint32_t *wg_cnt, uint32_t nwg, uint32_t words_per_wg,
-                               uint32_t nwords, uint32_t Mcap, uint32_t lag, uint32_t wbits, uint32_t *pos,
+hipError_t am_launch_gather_wg(const uint32_t *bits, const uint32_t *wg_cnt, const am_fe_layout &l, uint32_t Mcap, uint32_t *pos,
                                uint32_t *total_out, hipStream_t s, const am_rows_args *rows)
 {
+    const uint32_t nwg = l.nwg, words_per_wg = l.words_per_wg(), nwords = l.nwords(), lag = l.lag, wbits = l.wbits;
     if (nwg == 0) return hipSuccess;
-    if (wbits == 0 || wbits > 32 || words_per_wg == 0) return hipErrorInvalidValue;
+    if (wbits == 0 || wbits > 32 || words_per_wg == 0 || !l.alike()) return hipErrorInvalidValue;   // (one segment length: am_k_refine_seg places two)
     am_rows_args ra;
     memset(&ra, 0, sizeof(ra));
     if (rows && rows->iq) {
@@ -1189,9 +1189,10 @@ am_k_refine_late(const float *__restrict__ bb, const float *__restrict__ avg_spa
 
 hipError_t am_launch_refine_late(const float *bb, const float *avg_sparse, const uint32_t *pos, uint32_t M, int spc,
                                  float thr_lin, uint32_t end_j, uint32_t *e, uint32_t *tgt, float *inavg, uint8_t *valid,
-                                 uint32_t *jump0, hipStream_t s, const uint32_t *Mp, const float *vmax, uint32_t vspan,
-                                 uint32_t nv, const float *bb_max)
+                                 uint32_t *jump0, hipStream_t s, const uint32_t *Mp, const float *vmax, const am_fe_layout &l,
+                                 const float *bb_max)
 {
+    const uint32_t vspan = l.vspan(), nv = l.nv();
     if (M == 0) return hipSuccess;
     if (spc > 32 || spc < 1 || !vmax || vspan == 0 || nv == 0 || !jump0) return hipErrorInvalidValue;   // (the rounding bound is stated for 4 spc <= 128 terms)
     if (bb_max && (spc != 32 || (reinterpret_cast<uintptr_t>(bb) & 15u) != 0)) return hipErrorInvalidValue;   // (rows of 32 samples, 16-byte aligned)

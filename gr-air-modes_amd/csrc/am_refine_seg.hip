@@ -747,25 +747,25 @@ __global__ void __launch_bounds__(RS_NT, RS_WPS) am_k_refine_seg(am_rseg_args a)
 #endif
 }
 
-hipError_t am_launch_refine_seg(const uint32_t *bits, const uint32_t *wg_cnt, const float *wg_max, uint32_t nwg, uint32_t n_long,
-                                uint32_t words_per_wg, uint32_t words_per_step, uint32_t nwords, uint32_t Mcap, uint32_t lag, uint32_t wbits, uint32_t vspan, uint32_t nv,
+hipError_t am_launch_refine_seg(const uint32_t *bits, const uint32_t *wg_cnt, const float *wg_max, const am_fe_layout &l, uint32_t Mcap,
                                 const am_rows_args &rows, const float *avg_sparse, float thr_lin, uint32_t end_j, uint32_t *pos,
                                 uint32_t *e, uint32_t *tgt, float *inavg, uint8_t *valid, uint32_t *jump0, uint32_t *total_out,
                                 hipStream_t s)
 {
-    if (nwg == 0 || nwords == 0) return hipSuccess;
+    const uint32_t nwg = l.nwg, words_per_wg = l.words_per_wg();
+    if (nwg == 0 || l.nwords() == 0) return hipSuccess;
     // (am_k_fe3's bitmap: a word = one 32-sample chip, lag 288)
-    if (wbits != 32 || lag != 288 || words_per_wg == 0 || !rows.iq || vspan == 0 || nv == 0) return hipErrorInvalidValue;
+    if (l.wbits != 32 || l.lag != 288 || words_per_wg == 0 || !rows.iq || l.vspan() == 0 || l.nv() == 0) return hipErrorInvalidValue;
+    if (!l.alike() && l.words_short() == 0) return hipErrorInvalidValue;   // (levelled: the short segments have a step too)
     am_rseg_args a;
-    a.bits = bits; a.wg_cnt = wg_cnt; a.wg_max = wg_max; a.nwg = nwg; a.words_per_wg = words_per_wg; a.nwords = nwords; a.Mcap = Mcap;
-    a.vspan = vspan; a.nv = nv; a.end_j = end_j; a.iq = rows.iq; a.src_abs0 = rows.src_abs0; a.src_abs1 = rows.src_abs1;
+    a.bits = bits; a.wg_cnt = wg_cnt; a.wg_max = wg_max; a.nwg = nwg; a.words_per_wg = words_per_wg; a.nwords = l.nwords(); a.Mcap = Mcap;
+    a.vspan = l.vspan(); a.nv = l.nv(); a.end_j = end_j; a.iq = rows.iq; a.src_abs0 = rows.src_abs0; a.src_abs1 = rows.src_abs1;
     a.out_abs0 = rows.out_abs0; a.avg_sparse = avg_sparse; a.s1 = rows.s1; a.thr_lin = thr_lin; a.pos = pos; a.e = e; a.tgt = tgt;
     a.jump0 = jump0; a.total_out = total_out; a.inavg = inavg; a.valid = valid;
-    // levelled segments: the first n_long of words_per_wg words, the others one step shorter (n_long = 0 or >= nwg: all alike)
-    a.n_long = (n_long == 0 || n_long > nwg) ? nwg : n_long;
-    if (a.n_long < nwg && (words_per_step == 0 || words_per_step >= words_per_wg)) return hipErrorInvalidValue;
-    a.words_short = a.n_long < nwg ? words_per_wg - words_per_step : words_per_wg;
-    a.vspan_short = a.n_long < nwg ? (uint32_t)((unsigned long long)vspan * a.words_short / words_per_wg) : vspan;
+    // levelled segments: the first n_long of words_per_wg words, the others one step shorter
+    a.n_long = l.alike() ? nwg : l.n_long;
+    a.words_short = l.words_short();
+    a.vspan_short = l.vspan_short();
     // shares of a segment: about RS_PW words each, at most RS_MAXPARTS (longer segments: several windows per share)
     a.parts = (words_per_wg + RS_PW - 1) / RS_PW;
     if (a.parts > RS_MAXPARTS) a.parts = RS_MAXPARTS;

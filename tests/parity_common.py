@@ -364,6 +364,84 @@ def check_one_context_every_tail(lib, rate):
     return len(want)
 
 
+def check_one_context_every_front(lib, rate):
+    """Every way of starting a scan on the SAME context, one after the other (lib: a build with the test knobs, created under
+    AIRMODES_SPEC_FLOOR=0): a streamed scan in three cuts, the dense front end, the block-level preamble, a speculative scan that
+    outgrows its capacity and is redone, another sample rate (5 Msps: the rate-generic kernels) and back, K streams in one scan,
+    a submitted batch, and the streamed scan again.  Whatever one front half left in the context for its tail -- count or capacity,
+    dense or sparse bb, the samples, the bitmap's layout, the refinement request -- would show in the next: every step is
+    compared with the oracle.  64 Msps: also inputs of 9, 13 and 14 front-end steps, where am_k_fe3's levelled grid has two
+    segment lengths on any device (2, 3, 3 workgroups with 1, 1, 2 long ones), down to the first-stage candidate records."""
+    import ctypes as C
+    spc = int(rate / 2e6)
+    thr, pmf = 7.0, True
+    iq, _ = synth.synth_capture(rate, 20000 * spc, 6000.0, 3)
+    n = len(iq)
+    want = oracle.demod(iq, rate, thr, pmf)
+    assert len(want) >= 20
+    device = -1 if bool(getattr(lib, "emulated", False)) else 0
+    c = _capi.Context(rate, thr, pmf, device=device, lib=lib)
+
+    def streamed(step):
+        cuts = [0, n // 3, 2 * n // 3 + 7, n]
+        got = np.concatenate([c.process_iq(iq[a:b], flush=(b == n)) for a, b in zip(cuts[:-1], cuts[1:])])
+        assert got.tobytes() == want.tobytes(), "step %d: %d vs %d packets" % (step, len(got), len(want))
+        assert c.last_frontend() == 3
+
+    # 1. a streamed scan in three cuts
+    streamed(1)
+    # 2. the dense front end
+    obb, oavg = oracle.frontend(iq, spc, pmf)
+    bb, avg = c.frontend_work(iq)
+    assert np.array_equal(u32(bb), u32(obb)) and np.array_equal(u32(avg), u32(oavg)), "step 2: bb / avg differ"
+    # 3. the block-level preamble on the oracle's bb / avg
+    bursts, tags = c.preamble_work(obb, oavg)
+    ob, ot = oracle.preamble_scan(obb, oavg, spc, thr, rate)
+    assert len(ot) >= 20 and np.ascontiguousarray(tags).tobytes() == np.ascontiguousarray(ot).tobytes(), "step 3: tags differ"
+    assert np.array_equal(u32(bursts), u32(ob)), "step 3: bursts differ"
+    # 4. a quiet stretch, then a dense one, no slack: the dense scan is launched for 1.25 x the quiet one's candidate density,
+    # meets several times as many and is redone with the exact count
+    quiet, _ = synth.synth_capture(rate, n, 300.0, 5)
+    both = np.concatenate([quiet, iq])
+    got = [c.process_iq(both[:n])]
+    m_quiet = c.last_num_candidates()
+    got.append(c.process_iq(both[n:], flush=True))
+    m_dense = c.last_num_candidates()
+    assert m_quiet >= 1 and m_dense > 4 * m_quiet, "step 4: %d then %d candidates: no overflow" % (m_quiet, m_dense)
+    assert np.concatenate(got).tobytes() == oracle.demod(both, rate, thr, pmf).tobytes(), "step 4: packets differ"
+    # 5. 5 Msps (2.5 samples per chip: the rate-generic kernels), and back
+    iq5, _ = synth.synth_capture(5e6, 50000, 6000.0, 4)
+    want5 = oracle.demod(iq5, 5e6, thr, pmf)
+    c.set_rate(5e6)
+    got5 = c.process_iq(iq5, flush=True)
+    assert len(want5) >= 20 and got5.tobytes() == want5.tobytes(), "step 5: %d vs %d packets" % (len(got5), len(want5))
+    assert c.last_frontend() == 1
+    c.set_rate(rate)
+    # 6. K = 3 streams in one scan
+    streams = [iq[: n // 2], iq[n // 3:], iq[n // 4: 3 * n // 4 + 5]]
+    buf, lens = c.multi_pack(streams)
+    for j, (g, s) in enumerate(zip(c.process_multi(buf, lens), streams)):
+        w = oracle.demod(s, rate, thr, pmf)
+        assert len(w) >= 5 and g.tobytes() == w.tobytes(), "step 6: stream %d: %d vs %d packets" % (j, len(g), len(w))
+    # 7. a submitted batch, collected later
+    f = np.ascontiguousarray(iq).view(np.float32)
+    out, got_n = np.zeros(len(want) + 8, _capi.PACKET_DTYPE), C.c_uint64(0)
+    assert lib.L.am_submit_iq(c._h, f.ctypes.data, n, _capi.AM_F_FLUSH) == _capi.AM_OK
+    assert lib.L.am_collect(c._h, out.ctypes.data, len(out), C.byref(got_n)) == _capi.AM_OK
+    assert out[: got_n.value].tobytes() == want.tobytes(), "step 7: %d vs %d packets" % (got_n.value, len(want))
+    # 8. ... and the streamed scan again
+    streamed(8)
+    if spc == 32:
+        for k, a in ((9, 0), (13, n // 3), (14, n // 2)):
+            cut = iq[a: a + k * 3072 - 288]              # ceil((samples + 288) / 3072) = k steps
+            w = oracle.demod(cut, rate, thr, pmf)
+            g = c.process_iq(cut, flush=True)
+            assert g.tobytes() == w.tobytes(), "%d steps: %d vs %d packets" % (k, len(g), len(w))
+            check_production_stages(lib, rate, 0, 0.0, 0, thr, pmf, want_fe=3, iq=cut)
+    c.close()
+    return len(want)
+
+
 def check_stream_sharded(lib, rate, iq, W, K, thr=7.0, pmf=True, want=None, dcblock=False):
     if want is None:
         want = oracle.demod(iq, rate, thr, pmf, use_dcblock=dcblock)

@@ -497,3 +497,11 @@ def test_steps_in_flight_over_w_ranks_in_one_process(emu_lib, rate, W, K, m, sma
 def test_one_context_every_tail(emu_lib, rate):
     """Two contexts through every kind of scan tail in turn (pc.check_one_context_every_tail): nothing a tail was told survives it."""
     assert pc.check_one_context_every_tail(emu_lib, rate) >= 20
+
+
+@pytest.mark.parametrize("rate", [8e6, 64e6])
+def test_one_context_every_front(emu_lib, monkeypatch, rate):
+    """One context through every way of starting a scan in turn (pc.check_one_context_every_front): nothing a front half left for
+    its tail survives into the next scan."""
+    monkeypatch.setenv("AIRMODES_SPEC_FLOOR", "0")
+    assert pc.check_one_context_every_front(emu_lib, rate) >= 20

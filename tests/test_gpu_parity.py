@@ -585,3 +585,10 @@ def test_steps_in_flight_over_w_ranks_on_device(hip_lib, oracle_mod, rate, W, K,
 def test_one_context_every_tail_on_device(hip_lib, oracle_mod, rate):
     """Two contexts through every kind of scan tail in turn on the GPU (pc.check_one_context_every_tail)."""
     assert pc.check_one_context_every_tail(hip_lib, rate) >= 20
+
+
+@pytest.mark.parametrize("rate", [8e6, 64e6])
+def test_one_context_every_front_on_device(klib, oracle_mod, monkeypatch, rate):
+    """One context through every way of starting a scan in turn on the GPU (pc.check_one_context_every_front)."""
+    monkeypatch.setenv("AIRMODES_SPEC_FLOOR", "0")
+    assert pc.check_one_context_every_front(klib, rate) >= 20

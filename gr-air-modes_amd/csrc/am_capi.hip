@@ -199,6 +199,9 @@ struct am_ctx {
         cblk_cnt, cblk_off, scalars, bursts, tags, packets, crc_pow, recs, cscratch, dc_m1, dc_y, wgmax;
     int fe_wgs_per_cu = 0;                // persistent front-end workgroups per CU (0: as many as fit; am_pipe: one fewer)
     DevBuf lb_dc, lb_mark;      // slots of the chained scans (am_chain_prefix): zero at allocation, tagged with lb_epoch
+    DevBuf lb_entry;            // ... and of the block entries the walker of am_k_cblk_visit hands its markers ({epoch, entry} per block)
+    int walk_mode = AM_WALK_AUTO;   // test builds: AIRMODES_WALK forces the one- or the two-launch form of the chain visit
+    bool walk_clear = false;        // chain_prepare has cleared scalars[0 .. 1] and no visit has raised them since (the one-launch form needs it)
     uint32_t lb_epoch = 0;
     uint32_t tk_base[2] = {0, 0};     // value of the ticket counters scalars[10], [11] when the next launch on them starts (am_chain_place)
 
@@ -288,7 +291,7 @@ int ensure_slots(am_ctx *c, DevBuf &b, size_t n)
 uint32_t next_epoch(am_ctx *c)
 {
     if (++c->lb_epoch == 0) {
-        for (DevBuf *b : {&c->lb_dc, &c->lb_mark})
+        for (DevBuf *b : {&c->lb_dc, &c->lb_mark, &c->lb_entry})
             if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap, c->stream);
         c->lb_epoch = 1;
     }
@@ -807,7 +810,9 @@ int chain_prepare(am_ctx *c, bool want_last)
     if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
     ENSURE(c, c->cscratch, am_chain_scratch_bytes(M));
     HIPCHK(c, am_launch_chain_prepare((uint32_t *)c->pos.p, (uint32_t *)c->tgt.p, M, (uint32_t *)c->jump.p,
-                                      (uint32_t *)c->cscratch.p, want_last ? 1 : 0, c->stream, Mp, c->scan.jump_ready ? 1 : 0));
+                                      (uint32_t *)c->cscratch.p, want_last ? 1 : 0, c->stream, Mp, c->scan.jump_ready ? 1 : 0,
+                                      (uint32_t *)c->scalars.p));
+    c->walk_clear = true;
     return AM_OK;
 }
 
@@ -882,13 +887,26 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
     uint32_t *n_ptr = (uint32_t *)c->cblk_off.p + nb;
     ENSURE(c, c->emit_idx, (size_t)n_max * sizeof(uint4));     // one record per hit: {candidate, position, refined position, reference level}
     if (int rc = ensure_slots(c, c->lb_mark, nb); rc != AM_OK) return rc;
-    // which candidates the scan visits, which of them are hits, and their ordered list -- one launch after the walk
+    // which candidates the scan visits, which of them are hits, and their ordered list -- one launch with the walk for a plain
+    // synchronous scan (no entry source, no walk event; am_launch_chain_visit decides on the size), one launch after the walk
+    // otherwise.  A DEFERRED tail (am_submit_iq, am_pipe_*) keeps the two launches: with batches in flight the fused kernel's
+    // workgroups -- 1024 threads and the walk's tables in LDS, one per CU -- wait for CUs the other contexts' front ends hold,
+    // and the step got slower, not faster (profiles/walk_in_mark/ab_walk_in_mark.txt: pipelined 0.226 -> 0.228-0.235 ms)
+    const bool may_fuse = c->walk_clear && !req.has_entry && !req.walk_event && (!req.defer || c->walk_mode == AM_WALK_FUSED);
+    if (may_fuse)
+        if (int rc = ensure_slots(c, c->lb_entry, nb); rc != AM_OK) return rc;
+    c->walk_clear = false;
+    int fused = 0;
     HIPCHK(c, am_launch_chain_visit((uint32_t *)c->pos.p, (uint32_t *)c->jump.p, M, cur0, (uint32_t *)c->cscratch.p,
                                     (uint8_t *)c->valid.p, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p, emit_max, req.own_lo,
                                     req.own_hi, (uint4 *)c->emit_idx.p, n_ptr, (unsigned long long *)c->lb_mark.p,
                                     next_epoch(c), (uint32_t *)c->scalars.p + 11, &c->tk_base[1],
                                     (uint32_t *)c->scalars.p, emit_max == 0xFFFFFFFFu ? 1 : 0, c->stream, Mp,
-                                    req.has_entry ? &req.entry : nullptr, (const float *)c->inavg.p, req.walk_event));
+                                    req.has_entry ? &req.entry : nullptr, (const float *)c->inavg.p, req.walk_event,
+                                    may_fuse ? (unsigned long long *)c->lb_entry.p : nullptr, c->walk_mode, &fused));
+#if defined(AM_TEST_KNOBS)
+    if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: chain visit %s, %u blocks\n", fused ? "fused" : "separate", (M + 2047u) / 2048u);
+#endif
     const bool keep_dev = keep_bursts || req.keep_tags;      // the bursts and their tags leave the kernel
     if (keep_dev) ENSURE(c, c->bursts, (size_t)n_max * AM_BURST * sizeof(float));
     if (c->pin_cap < n_max) {
@@ -1156,6 +1174,8 @@ am_ctx *am_create(int device, double rate, float threshold_db, int use_pmf, int 
             const char *sp = getenv("AIRMODES_NO_SPEC");
             c->allow_spec = !(sp && sp[0] == '1');
             if (const char *sf = getenv("AIRMODES_SPEC_FLOOR")) c->spec_floor = atof(sf);
+            if (const char *wk = getenv("AIRMODES_WALK"))
+                c->walk_mode = !strcmp(wk, "separate") ? AM_WALK_SEPARATE : !strcmp(wk, "fused") ? AM_WALK_FUSED : AM_WALK_AUTO;
         }
 #endif
         if ((code = configure_rate(c, rate)) != AM_OK) {
@@ -1200,7 +1220,7 @@ void am_destroy(am_ctx *c)
     DevBuf *all[] = {&c->raw_in, &c->pb_bb, &c->pb_avg, &c->bbmax, &c->carry, &c->carry2, &c->src, &c->bb, &c->avg, &c->cand_seg, &c->inavg, &c->dcount, &c->off_local, &c->blk_tot2, &c->blk_base2,
                      &c->energy, &c->bits, &c->seg_base, &c->blk_cnt, &c->blk_off,
                      &c->pos, &c->e, &c->tgt, &c->valid, &c->jump, &c->emit_idx,
-                     &c->lb_dc, &c->lb_mark, &c->cblk_cnt, &c->cblk_off, &c->scalars, &c->bursts, &c->tags, &c->packets, &c->crc_pow,
+                     &c->lb_dc, &c->lb_mark, &c->lb_entry, &c->cblk_cnt, &c->cblk_off, &c->scalars, &c->bursts, &c->tags, &c->packets, &c->crc_pow,
                      &c->recs, &c->cscratch, &c->dc_m1, &c->dc_y, &c->tt_dev, &c->wgmax, &c->shard_exit, &c->chip_idx,
                      &c->gate_rec, &c->gate_scratch, &c->gate_map, &c->gate_multi};
     for (DevBuf *b : all) release(*b);

@@ -225,7 +225,8 @@ hipError_t am_launch_refine(const float *bb, const float *avg, const am_geom &g,
 size_t am_chain_scratch_bytes(uint32_t M);
 hipError_t am_launch_chain_prepare(const uint32_t *pos, const uint32_t *tgt, uint32_t M, uint32_t *jump0,
                                    uint32_t *scratch, int want_last, hipStream_t s, const uint32_t *Mp = nullptr,
-                                   int have_succ = 0);   /* have_succ: jump0[] was written by am_k_cand */
+                                   int have_succ = 0, uint32_t *scalars = nullptr);   /* have_succ: jump0[] was written by am_k_cand;
+                                   scalars: its words [0 .. 1] are cleared (what the one-launch form of am_launch_chain_visit starts from) */
 /* where the greedy scan of a time shard starts: composed on the device from everybody's exit tables (am_k_cblk_walk) */
 struct am_entry_src {
     const am_shard_exit *msgs = nullptr;      // null: the start position comes from the host
@@ -237,13 +238,17 @@ struct am_entry_src {
     const uint64_t *cur_in = nullptr;   // non-null: where the scan left the chunk BEFORE this one, read when the entry is composed (am_spipe)
 };
 
+enum { AM_WALK_AUTO = 0, AM_WALK_SEPARATE = 1, AM_WALK_FUSED = 2 };   /* walk_mode: test builds force a form (AIRMODES_WALK) */
 hipError_t am_launch_chain_visit(const uint32_t *pos, const uint32_t *jump0, uint32_t M, uint32_t cur0,
                                  uint32_t *scratch, const uint8_t *valid, const uint32_t *e, const uint32_t *tgt,
                                  uint32_t emit_max, uint32_t own_lo, uint32_t own_hi, uint4 *emit_idx, uint32_t *n_out,
                                  unsigned long long *slots, uint32_t epoch, uint32_t *ticket, uint32_t *ticket_base,
                                  uint32_t *scalars, int want_resume,
                                  hipStream_t s, const uint32_t *Mp, const am_entry_src *entry_src, const float *inavg,
-                                 hipEvent_t after_walk = nullptr);
+                                 hipEvent_t after_walk = nullptr, unsigned long long *entry_slots = nullptr,
+                                 int walk_mode = AM_WALK_AUTO, int *fused_out = nullptr);
+/* (entry_slots: one 64-bit word per block, zero at allocation, tagged with `epoch` like slots -- given, and with neither an entry
+ * source nor a walk event, walk and marking are ONE launch whenever its workgroups are resident at once; null: two launches) */
 /* (emit_idx: one 16-byte record per hit -- candidate index, first-stage position, refined position, reference level -- so that
  * the extraction kernels fetch a hit with one load) */
 /* lead_end (array coordinate): the table is only needed up to the first candidate at or past it */

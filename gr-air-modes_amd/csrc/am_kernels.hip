@@ -1249,11 +1249,15 @@ am_k_chain_succ(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ t
 
 __global__ void __launch_bounds__(AM_CB_THREADS)
 am_k_cblk_exit(const uint32_t *__restrict__ jump0, uint32_t Mcap, uint32_t headw, uint32_t *__restrict__ exitnode,
-               uint32_t *__restrict__ lastnode, uint16_t *__restrict__ headlink, const uint32_t *__restrict__ Mp)
+               uint32_t *__restrict__ lastnode, uint16_t *__restrict__ headlink, const uint32_t *__restrict__ Mp,
+               uint32_t *__restrict__ scalars)
 {
     __shared__ uint32_t e[2][AM_CB];           // orbit node 2^r hops ahead, clipped to the first one outside
     __shared__ uint32_t l[2][AM_CB];           // the orbit node just before it (always inside the block)
     const uint32_t M = am_count(Mcap, Mp);
+    // resume position and hit flag start from zero a launch AHEAD of the one that raises them: inside am_k_cblk_visit the
+    // walker's cur0 and the markers' targets are atomics from different XCDs, and a plain store among them is not ordered
+    if (scalars && blockIdx.x == 0 && threadIdx.x == 0) { scalars[0] = 0u; scalars[1] = 0u; }
     const uint32_t base = blockIdx.x * AM_CB;
     if (base >= M) {                                          // (capacity launch: nothing here)
         for (uint32_t i = threadIdx.x; i < headw; i += blockDim.x) headlink[(size_t)blockIdx.x * headw + i] = (uint16_t)AM_CB_END;
@@ -1440,43 +1444,30 @@ __device__ __forceinline__ uint64_t am_shard_entry_wave(const am_shard_exit *__r
 // (3) in parallel, one lane per group repeats the hops inside its group from the slot (2) found and records the
 // entry node of each block.  Global memory only for the root, for a link that lands beyond a head, and for an
 // unusually long head (ki >= headw): those go hop by hop in step (2).
-__global__ void __launch_bounds__(1024)
-am_k_cblk_walk(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ exitnode,
-               const uint16_t *__restrict__ headlink, uint32_t Mcap, uint32_t nblk, uint32_t headw, uint32_t cur0_host,
-               uint32_t *__restrict__ entry, uint32_t *__restrict__ scalars, const uint32_t *__restrict__ Mp,
-               am_entry_src es)
+// The body of the walk, for am_k_cblk_walk and for the walker of am_k_cblk_visit (FUSED).  All 1024 threads call it; lnk = dynamic
+// LDS (am_chain_walk_lds_bytes), *cur0_sh = the scan's start position (written before the call, read behind the first barrier).
+// FUSED: every block's entry also goes out as one {epoch, entry} word (entw[]: the payload-in-word pattern of am_chain_prefix,
+// relaxed device-scope stores, never reset), and scalars[0] is RAISED to cur0 with the markers' own atomic (am_k_cblk_exit
+// cleared it a launch ahead).
+template <bool FUSED>
+__device__ __forceinline__ void am_cblk_walk_body(uint16_t *lnk, uint32_t *seg_sh, uint32_t *root_sh, const uint32_t *cur0_sh,
+                                                  const uint32_t *__restrict__ pos, const uint32_t *__restrict__ exitnode,
+                                                  const uint16_t *__restrict__ headlink, uint32_t M, uint32_t nblk, uint32_t headw,
+                                                  uint32_t *__restrict__ entry, uint32_t *__restrict__ scalars,
+                                                  unsigned long long *entw, uint32_t epoch)
 {
-    const uint32_t M = am_count(Mcap, Mp);
-    // time shards: the position at which the scan enters this chunk is composed here, from everybody's exit tables, by the
-    // first wave -- while the other waves fetch the link table (a launch of its own cost 4.4 us + the gap behind it)
-    __shared__ uint32_t cur0_s;
-    if (es.msgs) {
-        if (threadIdx.x < AM_WAVE) {
-            uint32_t bad = 0;
-            uint64_t leave = 0;
-            const uint64_t cur = am_shard_entry_wave(es.msgs, es.world, es.rank, es.cap, (int)threadIdx.x, &bad, &leave, es.cur_in, es.carry_out);
-            if (threadIdx.x == 0) {
-                uint64_t rel = cur > es.base_abs ? cur - es.base_abs : 0;
-                if (rel > 0xFFFFFFF0ull) rel = 0xFFFFFFF0ull;
-                cur0_s = (uint32_t)rel;
-                es.flags[0] = bad;                           // (written either way: nobody has to clear it first)
-                if (!bad) *es.exit_out = leave;              // where the scan leaves this chunk: the next step's message carries it
-            }
-        }
-    } else if (threadIdx.x == 0)
-        cur0_s = cur0_host;
+    uint32_t &seg = *seg_sh, &root_s = *root_sh;
 #if defined(AM_WALK_DEBUG)
     int wdbg[5] = {0, 0, 0, 0, 0};
     long long wclk[5] = {0, 0, 0, 0, 0};
     AM_WALK_CLOCK(0);
 #endif
-    HIP_DYNAMIC_SHARED(uint16_t, lnk);         // [nblk * headw (+pad to 8)] links | [nblk] entry index | [ngrp * headw] group exits | [ngrp] group entry slots
+    // lnk: [nblk * headw (+pad to 8)] links | [nblk] entry index | [ngrp * headw] group exits | [ngrp] group entry slots
     const uint32_t total = nblk * headw;
     const uint32_t ngrp = (nblk + AM_CB_GROUP - 1u) / AM_CB_GROUP;
     uint16_t *ent = lnk + ((total + 7u) & ~7u);
     uint16_t *gex = ent + nblk;
     uint16_t *gin = gex + ngrp * headw;
-    __shared__ uint32_t seg, root_s;
     // root = first candidate with pos >= cur0, in two parallel rounds (two dependent loads in all): which of 1024
     // equal segments holds it, then which node of that segment.  The first round's loads go out together with the
     // table's.
@@ -1490,8 +1481,11 @@ am_k_cblk_walk(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ ex
     for (uint32_t bb = threadIdx.x; bb < nblk; bb += blockDim.x) ent[bb] = (uint16_t)AM_CB_END;
     for (uint32_t gg = threadIdx.x; gg < ngrp; gg += blockDim.x) gin[gg] = (uint16_t)AM_CB_END;
     __syncthreads();
-    const uint32_t cur0 = cur0_s;
-    if (threadIdx.x == 0) { scalars[0] = cur0; scalars[1] = 0u; }
+    const uint32_t cur0 = *cur0_sh;
+    if (threadIdx.x == 0) {
+        if (FUSED) { if (cur0) atomicMax(&scalars[0], cur0); }
+        else { scalars[0] = cur0; scalars[1] = 0u; }
+    }
     if (stride && lo < M && p_hi >= cur0 && (lo == 0 || p_lo < cur0)) seg = lo;
     __syncthreads();
     for (uint32_t g = seg + threadIdx.x; g < M && g < seg + stride; g += blockDim.x)
@@ -1575,8 +1569,43 @@ am_k_cblk_walk(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ ex
     if (threadIdx.x == 0) AM_WALK_REPORT();
     for (uint32_t bb = threadIdx.x; bb < nblk; bb += blockDim.x) {
         const uint32_t ki = ent[bb];
-        entry[bb] = (ki == AM_CB_END) ? AM_CB_NONE : bb * AM_CB + ki;
+        const uint32_t en = (ki == AM_CB_END) ? AM_CB_NONE : bb * AM_CB + ki;
+        entry[bb] = en;
+        if (FUSED)
+            __hip_atomic_store(&entw[bb], ((unsigned long long)epoch << 32) | (unsigned long long)en, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+
+__global__ void __launch_bounds__(1024)
+am_k_cblk_walk(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ exitnode,
+               const uint16_t *__restrict__ headlink, uint32_t Mcap, uint32_t nblk, uint32_t headw, uint32_t cur0_host,
+               uint32_t *__restrict__ entry, uint32_t *__restrict__ scalars, const uint32_t *__restrict__ Mp,
+               am_entry_src es)
+{
+    const uint32_t M = am_count(Mcap, Mp);
+    // time shards: the position at which the scan enters this chunk is composed here, from everybody's exit tables, by the
+    // first wave -- while the other waves fetch the link table (a launch of its own cost 4.4 us + the gap behind it)
+    __shared__ uint32_t cur0_s;
+    if (es.msgs) {
+        if (threadIdx.x < AM_WAVE) {
+            uint32_t bad = 0;
+            uint64_t leave = 0;
+            const uint64_t cur = am_shard_entry_wave(es.msgs, es.world, es.rank, es.cap, (int)threadIdx.x, &bad, &leave, es.cur_in, es.carry_out);
+            if (threadIdx.x == 0) {
+                uint64_t rel = cur > es.base_abs ? cur - es.base_abs : 0;
+                if (rel > 0xFFFFFFF0ull) rel = 0xFFFFFFF0ull;
+                cur0_s = (uint32_t)rel;
+                es.flags[0] = bad;                           // (written either way: nobody has to clear it first)
+                if (!bad) *es.exit_out = leave;              // where the scan leaves this chunk: the next step's message carries it
+            }
+        }
+    } else if (threadIdx.x == 0)
+        cur0_s = cur0_host;
+    HIP_DYNAMIC_SHARED(uint16_t, lnk);
+    __shared__ uint32_t seg, root_s;
+    am_cblk_walk_body<false>(lnk, &seg, &root_s, &cur0_s, pos, exitnode, headlink, M, nblk, headw, entry, scalars, nullptr, 0u);
 }
 
 // Exit table of a time chunk (am_shard_scan): for each of the chunk's first n candidates, the scan
@@ -1696,15 +1725,22 @@ struct am_emit_args {
     int want_resume;
 };
 
-__global__ void __launch_bounds__(AM_CB_THREADS)
-am_k_cblk_mark(const uint32_t *__restrict__ jump0, const uint32_t *__restrict__ entry, uint32_t Mcap,
-               am_emit_args ea, const uint32_t *__restrict__ Mp)
+// The marking of one block, for am_k_cblk_mark (NT = 256 threads, the block's entry known when it starts) and for the markers
+// of am_k_cblk_visit (FUSED: NT = 1024, the entry arrives from the walker of the SAME launch).  NT / 64 waves, AM_CB / NT nodes
+// per thread, node order (k, wave, lane) either way.  J / V / wc / wmax / red / ent_sh: LDS of the calling kernel.
+// FUSED: everything that does not depend on the entry comes first -- the successors, ALL hop levels (the early stop below
+// looks at J[l][entry]), the loads of the nodes' records -- and only then thread 0 polls the block's {epoch, entry} word
+// (am_cblk_walk_body<true> stores it: relaxed device-scope, the word carries its payload, so no fence on either side) and
+// hands the value round through LDS.  The walker holds place 0 of the launch's tickets, so it is running whenever somebody
+// polls; should its word never come (AM_CHAIN_SPIN_MAX polls, ~2 s), the block goes on WITHOUT an entry -- no hits, no
+// stores -- and raises scalars[9]: AM_EHIP at the C ABI, as when am_chain_prefix gives up.
+template <int NT, bool FUSED>
+__device__ __forceinline__ void am_cblk_mark_body(const uint32_t *__restrict__ jump0, const uint32_t *__restrict__ entry,
+                                                  const unsigned long long *entw, uint32_t M, uint32_t blk, uint32_t nblk,
+                                                  const am_emit_args &ea, uint16_t (*J)[AM_CB], uint8_t *V,
+                                                  uint32_t (*wc)[NT / AM_WAVE], uint32_t *wmax, uint32_t *red, uint32_t *ent_sh)
 {
-    __shared__ uint16_t J[AM_CB_LEVELS][AM_CB];
-    __shared__ uint8_t V[AM_CB];
-    __shared__ uint32_t wc[AM_CB_PER][AM_CB_THREADS / AM_WAVE], wmax[AM_CB_THREADS / AM_WAVE];
-    __shared__ uint32_t red[AM_CB_THREADS / AM_WAVE];
-    __shared__ uint32_t tick;
+    constexpr int PER = AM_CB / NT, NW = NT / AM_WAVE;
 #if defined(AM_MARK_PROF)
     long long mp[8]; int mpn = 0;
 #define AM_MSTAMP() do { __syncthreads(); mp[mpn++] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
@@ -1712,106 +1748,128 @@ am_k_cblk_mark(const uint32_t *__restrict__ jump0, const uint32_t *__restrict__ 
 #else
 #define AM_MSTAMP() ((void)0)
 #endif
-    const uint32_t M = am_count(Mcap, Mp);
-    const uint32_t blk = am_chain_place(ea.ticket, ea.ticket_base, &tick);   // block of candidates = place in the chain
     const uint32_t base = blk * AM_CB;
-    const uint32_t ent = (base < M) ? entry[blk] : AM_CB_NONE;
+    uint32_t ent = AM_CB_NONE;
+    if (!FUSED) ent = (base < M) ? entry[blk] : AM_CB_NONE;
     const int lane = threadIdx.x & (AM_WAVE - 1), w = threadIdx.x / AM_WAVE;
-    uint32_t embits = 0, tmax = 0;                            // bit k: node threadIdx.x + k * AM_CB_THREADS is a hit
-    uint32_t hp[AM_CB_PER], he[AM_CB_PER];                    // position / refined position / reference level of the thread's nodes
-    float hav[AM_CB_PER];                                     // (what a hit's record carries; loaded with the flags below)
+    uint32_t embits = 0, tmax = 0;                            // bit k: node threadIdx.x + k * NT is a hit
+    uint32_t hp[PER], he[PER];                                // position / refined position / reference level of the thread's nodes
+    float hav[PER];                                           // (what a hit's record carries; loaded with the flags below)
 #pragma unroll
-    for (int k = 0; k < AM_CB_PER; ++k) { hp[k] = 0u; he[k] = 0u; hav[k] = 0.0f; }
-    if (ent != AM_CB_NONE) {                                  // (uniform; otherwise the scan jumps over this block or nothing is here)
+    for (int k = 0; k < PER; ++k) { hp[k] = 0u; he[k] = 0u; hav[k] = 0.0f; }
+    // (uniform; otherwise the scan jumps over this block or nothing is here.  FUSED: whether the scan jumps over it is not known yet)
+    if (FUSED ? base < M : ent != AM_CB_NONE) {
         const uint32_t end = (base + AM_CB < M) ? base + AM_CB : M;
         const uint32_t n = end - base;
         const uint16_t OUT = (uint16_t)AM_CB;                // "leaves the block"
         {
-            uint32_t j[AM_CB_PER];                            // (unconditional loads from clamped indices, all in flight at once)
+            uint32_t j[PER];                                  // (unconditional loads from clamped indices, all in flight at once)
 #pragma unroll
-            for (int k = 0; k < AM_CB_PER; ++k) {
-                const uint32_t i = threadIdx.x + k * AM_CB_THREADS;
+            for (int k = 0; k < PER; ++k) {
+                const uint32_t i = threadIdx.x + k * NT;
                 j[k] = jump0[base + (i < n ? i : n - 1u)];
             }
 #pragma unroll
-            for (int k = 0; k < AM_CB_PER; ++k) {
-                const uint32_t i = threadIdx.x + k * AM_CB_THREADS;
+            for (int k = 0; k < PER; ++k) {
+                const uint32_t i = threadIdx.x + k * NT;
                 J[0][i] = (i < n && j[k] < end) ? (uint16_t)(j[k] - base) : OUT;
                 V[i] = 0;
             }
         }
-        __syncthreads();
-        // links 2^l hops ahead, l = 1 .. : only as far as the orbit of the entry node needs them -- once J[l][entry] leaves the
-        // block, the orbit has at most 2^l nodes here
-        // (the thread's eight nodes side by side, as in am_k_cblk_exit: reads, dependent reads, stores)
-        AM_MSTAMP();                                          // 1: successors loaded
-        const uint32_t ent_l = ent - base;
-        int nlev = 1;                                         // levels J[0 .. nlev) exist
-        while (nlev < AM_CB_LEVELS && J[nlev - 1][ent_l] != OUT) {               // (uniform: every thread reads the same word)
-            const int l = nlev;
-            uint16_t t[AM_CB_PER], u[AM_CB_PER];
-#pragma unroll
-            for (int k = 0; k < AM_CB_PER; ++k) t[k] = J[l - 1][threadIdx.x + k * AM_CB_THREADS];
-#pragma unroll
-            for (int k = 0; k < AM_CB_PER; ++k) u[k] = J[l - 1][(t[k] == OUT) ? 0 : t[k]];
-#pragma unroll
-            for (int k = 0; k < AM_CB_PER; ++k) J[l][threadIdx.x + k * AM_CB_THREADS] = (t[k] == OUT) ? OUT : u[k];
-            ++nlev;
-            __syncthreads();
-        }
-        AM_MSTAMP();                                          // 2: levels built
-        // The orbit's q-th node (q = 0: the entry) is reached by the hops of q's binary digits, in any order (they are powers
-        // of one map): thread t enumerates q = t, t + 256, ... on its own -- up to 11 dependent LDS reads each, eight chains
-        // side by side, no barrier in between -- and marks what it reaches.  (Round 2 pushed the marks down level by level, 11
-        // more barrier-separated passes over the block: the same 4.5 us -- both are bound by the random 16-bit LDS gathers,
-        // 88 per thread.  Phase clocks of a -DAM_MARK_PROF build, us: successors 1.1, levels 3.0, orbit 4.5, the visited
-        // nodes' records 1.4, counts 0.7, waiting for the blocks before 0.4-3.4, index stores 2.)
-        {
-            uint32_t x[AM_CB_PER];
-#pragma unroll
-            for (int k = 0; k < AM_CB_PER; ++k) {
-                const uint32_t q = threadIdx.x + k * AM_CB_THREADS;
-                x[k] = (nlev < AM_CB_LEVELS && (q >> nlev) != 0u) ? (uint32_t)OUT : ent_l;   // (beyond the orbit's length)
-            }
-            for (int l = 0; l < nlev; ++l) {
-#pragma unroll
-                for (int k = 0; k < AM_CB_PER; ++k) {
-                    const uint32_t q = threadIdx.x + k * AM_CB_THREADS;
-                    const uint32_t nx = J[l][x[k] == OUT ? 0u : x[k]];
-                    if ((q >> l) & 1u) x[k] = (x[k] == OUT) ? (uint32_t)OUT : nx;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < AM_CB_PER; ++k)
-                if (x[k] != OUT) V[x[k]] = 1;
-        }
-        __syncthreads();
-        AM_MSTAMP();                                          // 3: orbit marked
         // which visited nodes are hits, and where the scan resumes after everything visited here: the largest
         // target (only needed when the stream continues)
         // (all of a thread's loads go out together, visited or not: written as one node after the other -- position, then
         // `valid`, then `e` behind the short-circuit, eight nodes in turn -- the kernel spent most of its time in up to 24
         // serial memory round trips per thread)
-        bool vis[AM_CB_PER];
-        uint32_t p[AM_CB_PER], ee[AM_CB_PER], tg[AM_CB_PER];
-        uint8_t va[AM_CB_PER];
+        uint32_t p[PER], ee[PER], tg[PER];
+        uint8_t va[PER];
+        auto load_records = [&]() {
 #pragma unroll
-        for (int k = 0; k < AM_CB_PER; ++k) {
-            const uint32_t i = threadIdx.x + k * AM_CB_THREADS;
+            for (int k = 0; k < PER; ++k) {
+                const uint32_t i = threadIdx.x + k * NT;
+                const uint32_t g = base + (i < n ? i : n - 1u);   // (a node of the block in any case: no branch around the loads)
+                p[k] = ea.pos[g];
+                va[k] = ea.valid[g];
+                ee[k] = ea.e[g];
+                tg[k] = ea.tgt[g];
+                hav[k] = ea.inavg[g];
+            }
+        };
+        if (FUSED) load_records();                            // (in flight while the levels are built and the entry is awaited)
+        __syncthreads();
+        // links 2^l hops ahead, l = 1 .. : only as far as the orbit of the entry node needs them -- once J[l][entry] leaves the
+        // block, the orbit has at most 2^l nodes here
+        // (the thread's nodes side by side, as in am_k_cblk_exit: reads, dependent reads, stores)
+        AM_MSTAMP();                                          // 1: successors loaded
+        int nlev = 1;                                         // levels J[0 .. nlev) exist
+        while (nlev < AM_CB_LEVELS && (FUSED || J[nlev - 1][ent - base] != OUT)) {   // (uniform: every thread reads the same word)
+            const int l = nlev;
+            uint16_t t[PER], u[PER];
+#pragma unroll
+            for (int k = 0; k < PER; ++k) t[k] = J[l - 1][threadIdx.x + k * NT];
+#pragma unroll
+            for (int k = 0; k < PER; ++k) u[k] = J[l - 1][(t[k] == OUT) ? 0 : t[k]];
+#pragma unroll
+            for (int k = 0; k < PER; ++k) J[l][threadIdx.x + k * NT] = (t[k] == OUT) ? OUT : u[k];
+            ++nlev;
+            __syncthreads();
+        }
+        AM_MSTAMP();                                          // 2: levels built
+        if (FUSED) {
+            if (threadIdx.x == 0) {
+                unsigned long long v = __hip_atomic_load(&entw[blk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                bool failed = false;
+                for (unsigned spins = 0; (uint32_t)(v >> 32) != ea.epoch; ++spins) {
+                    if (spins == AM_CHAIN_SPIN_MAX) { failed = true; break; }
+                    __builtin_amdgcn_s_sleep(1);
+                    v = __hip_atomic_load(&entw[blk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if (failed) ea.scalars[9] = 1u;
+                *ent_sh = failed ? AM_CB_NONE : (uint32_t)v;
+            }
+            __syncthreads();
+            ent = *ent_sh;
+            if (ent != AM_CB_NONE)                            // the early stop, behind the fact: levels the orbit does not need are not walked
+                for (int l = AM_CB_LEVELS - 1; l >= 1; --l)
+                    if (J[l - 1][ent - base] == OUT) nlev = l;
+        }
+        // The orbit's q-th node (q = 0: the entry) is reached by the hops of q's binary digits, in any order (they are powers
+        // of one map): thread t enumerates q = t, t + NT, ... on its own -- up to 11 dependent LDS reads each, the thread's chains
+        // side by side, no barrier in between -- and marks what it reaches.  (Round 2 pushed the marks down level by level, 11
+        // more barrier-separated passes over the block: the same 4.5 us -- both are bound by the random 16-bit LDS gathers,
+        // 88 per thread.  Phase clocks of a -DAM_MARK_PROF build at NT = 256, us: successors 1.1, levels 3.0, orbit 4.5, the visited
+        // nodes' records 1.4, counts 0.7, waiting for the blocks before 0.4-3.4, index stores 2.)
+        if (ent != AM_CB_NONE) {                              // (uniform; FUSED: the scan may jump over this block)
+            const uint32_t ent_l = ent - base;
+            uint32_t x[PER];
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const uint32_t q = threadIdx.x + k * NT;
+                x[k] = (nlev < AM_CB_LEVELS && (q >> nlev) != 0u) ? (uint32_t)OUT : ent_l;   // (beyond the orbit's length)
+            }
+            for (int l = 0; l < nlev; ++l) {
+#pragma unroll
+                for (int k = 0; k < PER; ++k) {
+                    const uint32_t q = threadIdx.x + k * NT;
+                    const uint32_t nx = J[l][x[k] == OUT ? 0u : x[k]];
+                    if ((q >> l) & 1u) x[k] = (x[k] == OUT) ? (uint32_t)OUT : nx;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < PER; ++k)
+                if (x[k] != OUT) V[x[k]] = 1;
+        }
+        __syncthreads();
+        AM_MSTAMP();                                          // 3: orbit marked
+        bool vis[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const uint32_t i = threadIdx.x + k * NT;
             vis[k] = i < n && V[i] != 0;
         }
+        if (!FUSED) load_records();
 #pragma unroll
-        for (int k = 0; k < AM_CB_PER; ++k) {
-            const uint32_t i = threadIdx.x + k * AM_CB_THREADS;
-            const uint32_t g = base + (i < n ? i : n - 1u);   // (a node of the block in any case: no branch around the loads)
-            p[k] = ea.pos[g];
-            va[k] = ea.valid[g];
-            ee[k] = ea.e[g];
-            tg[k] = ea.tgt[g];
-            hav[k] = ea.inavg[g];
-        }
-#pragma unroll
-        for (int k = 0; k < AM_CB_PER; ++k) {
+        for (int k = 0; k < PER; ++k) {
             const bool em = vis[k] && va[k] != 0 && ee[k] <= ea.emit_max && p[k] >= ea.own_lo && p[k] < ea.own_hi;
             if (vis[k] && ea.want_resume) tmax = tg[k] > tmax ? tg[k] : tmax;
             if (em) embits |= 1u << k;
@@ -1822,7 +1880,7 @@ am_k_cblk_mark(const uint32_t *__restrict__ jump0, const uint32_t *__restrict__ 
     // ordered compaction of the hits, in the same launch: counts per (round k, wave) -> this block's total -> the
     // totals of the blocks before it (am_chain_prefix) -> every hit's index in emit_idx[].  Node order is
     // (k, wave, lane).
-    for (int k = 0; k < AM_CB_PER; ++k) {
+    for (int k = 0; k < PER; ++k) {
         const unsigned long long m = __ballot((embits >> k) & 1u);
         if (lane == 0) wc[k][w] = (uint32_t)__popcll(m);
     }
@@ -1833,45 +1891,93 @@ am_k_cblk_mark(const uint32_t *__restrict__ jump0, const uint32_t *__restrict__ 
     if (lane == 0) wmax[w] = tmax;
     __syncthreads();
     uint32_t tot = 0;
-    for (int k = 0; k < AM_CB_PER; ++k)
-        for (int q = 0; q < AM_CB_THREADS / AM_WAVE; ++q) tot += wc[k][q];
+    for (int k = 0; k < PER; ++k)
+        for (int q = 0; q < NW; ++q) tot += wc[k][q];
     // Same-address atomics serialise (~11 ns each): one per workgroup.
     if (threadIdx.x == 0 && ea.want_resume) {
         uint32_t m = 0;
-        for (int k = 0; k < AM_CB_THREADS / AM_WAVE; ++k) m = wmax[k] > m ? wmax[k] : m;
+        for (int k = 0; k < NW; ++k) m = wmax[k] > m ? wmax[k] : m;
         if (m) atomicMax(&ea.scalars[0], m);
     }
     AM_MSTAMP();
     const uint32_t before = am_chain_prefix(ea.slots, blk, ea.epoch, tot, red);
     AM_MSTAMP();                                              // chain prefix
     if (before == AM_CHAIN_FAIL) {                            // (uniform) a place was never published: no stores, the error word, no hits
-        if (threadIdx.x == 0) { ea.scalars[9] = 1u; if (blk == gridDim.x - 1) *ea.n_out = 0u; }
+        if (threadIdx.x == 0) { ea.scalars[9] = 1u; if (blk == nblk - 1) *ea.n_out = 0u; }
         return;
     }
     uint32_t off = before;
 #pragma unroll
-    for (int k = 0; k < AM_CB_PER; ++k) {
+    for (int k = 0; k < PER; ++k) {
         const bool em = ((embits >> k) & 1u) != 0u;
         const unsigned long long m = __ballot(em);
         uint32_t o = off;
         for (int q = 0; q < w; ++q) o += wc[k][q];
         if (em) {
-            const uint32_t g = base + threadIdx.x + (uint32_t)k * AM_CB_THREADS;
+            const uint32_t g = base + threadIdx.x + (uint32_t)k * NT;
             uint4 rec;
             rec.x = g; rec.y = hp[k]; rec.z = he[k]; rec.w = __float_as_uint(hav[k]);
             ea.emit_idx[o + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = rec;
         }
-        for (int q = 0; q < AM_CB_THREADS / AM_WAVE; ++q) off += wc[k][q];
+        for (int q = 0; q < NW; ++q) off += wc[k][q];
     }
-    if (blk == gridDim.x - 1 && threadIdx.x == 0) *ea.n_out = before + tot;
+    if (blk == nblk - 1 && threadIdx.x == 0) *ea.n_out = before + tot;
 #if defined(AM_MARK_PROF)
     AM_MSTAMP();
-    if (threadIdx.x == 0 && (blk == 0 || blk == gridDim.x / 2 || blk == gridDim.x - 1 || blk == M / AM_CB)) {
-        printf("mark blk %u/%u ent %d:", blk, gridDim.x, ent != AM_CB_NONE);
+    if (threadIdx.x == 0 && (blk == 0 || blk == nblk / 2 || blk == nblk - 1 || blk == M / AM_CB)) {
+        printf("mark blk %u/%u ent %d:", blk, nblk, ent != AM_CB_NONE);
         for (int k = 1; k < mpn; ++k) printf(" %lld", mp[k] - mp[k - 1]);
         printf("  (10 ns units; start %lld)\n", mp[0] % 1000000);
     }
 #endif
+}
+
+__global__ void __launch_bounds__(AM_CB_THREADS)
+am_k_cblk_mark(const uint32_t *__restrict__ jump0, const uint32_t *__restrict__ entry, uint32_t Mcap,
+               am_emit_args ea, const uint32_t *__restrict__ Mp)
+{
+    __shared__ uint16_t J[AM_CB_LEVELS][AM_CB];
+    __shared__ uint8_t V[AM_CB];
+    __shared__ uint32_t wc[AM_CB_PER][AM_CB_THREADS / AM_WAVE], wmax[AM_CB_THREADS / AM_WAVE];
+    __shared__ uint32_t red[AM_CB_THREADS / AM_WAVE];
+    __shared__ uint32_t tick;
+    const uint32_t M = am_count(Mcap, Mp);
+    const uint32_t blk = am_chain_place(ea.ticket, ea.ticket_base, &tick);   // block of candidates = place in the chain
+    am_cblk_mark_body<AM_CB_THREADS, false>(jump0, entry, nullptr, M, blk, gridDim.x, ea, J, V, wc, wmax, red, nullptr);
+}
+
+// Walk and marking in ONE launch of nblk + 1 workgroups (the walk as a launch of its own: one workgroup on the whole device,
+// 16 us + the gap behind it, in front of a marking kernel that starts with 5 us of work which does not need the walk's result).
+// ROLES GO BY TICKET, never by blockIdx: place 0 of am_chain_place is the walker, place p >= 1 marks block p - 1.  Whoever
+// holds place 0 has drawn it, i.e. is running, and the walker itself waits for nobody: no marker can wait for a workgroup
+// that has not been dispatched, wherever the hardware puts them and in whatever order.  (A host that runs the workgroups
+// one after another -- the CPU emulation -- runs place 0 first: every later workgroup finds its word.)
+// The walker reads am_k_cblk_exit's tables across a KERNEL BOUNDARY, so nothing large has to become visible inside the launch:
+// what crosses from workgroup to workgroup is one 8-byte {epoch, entry} word per block (entw[]) and am_chain_prefix's counts.
+// 1024 threads (the walk's step 1), dynamic LDS = max(walk tables, J + V of the marking): one workgroup per CU, so the host takes
+// this kernel only while nblk + 1 <= the device's CUs (am_launch_chain_visit).
+#define AM_CB_VTHREADS 1024
+#define AM_CB_MARK_LDS (AM_CB_LEVELS * AM_CB * sizeof(uint16_t) + AM_CB)   /* J | V */
+__global__ void __launch_bounds__(AM_CB_VTHREADS)
+am_k_cblk_visit(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ exitnode, const uint16_t *__restrict__ headlink,
+                const uint32_t *__restrict__ jump0, uint32_t Mcap, uint32_t nblk, uint32_t headw, uint32_t cur0,
+                uint32_t *__restrict__ entry, unsigned long long *entw, am_emit_args ea, const uint32_t *__restrict__ Mp)
+{
+    HIP_DYNAMIC_SHARED(uint4, dyn);            // (16-byte aligned: the walker copies the link table 16 bytes at a time)
+    __shared__ uint32_t wc[AM_CB / AM_CB_VTHREADS][AM_CB_VTHREADS / AM_WAVE], wmax[AM_CB_VTHREADS / AM_WAVE];
+    __shared__ uint32_t red[AM_CB_VTHREADS / AM_WAVE];
+    __shared__ uint32_t tick, seg, root_s, cur0_s, ent_s;
+    const uint32_t M = am_count(Mcap, Mp);
+    const uint32_t place = am_chain_place(ea.ticket, ea.ticket_base, &tick);
+    if (place == 0u) {                                        // (uniform)
+        if (threadIdx.x == 0) cur0_s = cur0;
+        am_cblk_walk_body<true>(reinterpret_cast<uint16_t *>(dyn), &seg, &root_s, &cur0_s, pos, exitnode, headlink, M, nblk, headw,
+                                entry, ea.scalars, entw, ea.epoch);
+        return;
+    }
+    uint16_t (*J)[AM_CB] = reinterpret_cast<uint16_t (*)[AM_CB]>(dyn);
+    uint8_t *V = reinterpret_cast<uint8_t *>(J + AM_CB_LEVELS);
+    am_cblk_mark_body<AM_CB_VTHREADS, true>(jump0, nullptr, entw, M, place - 1u, nblk, ea, J, V, wc, wmax, red, &ent_s);
 }
 
 // compute units of the current device (cached per device: a process may hold contexts on several)
@@ -1939,43 +2045,67 @@ static hipError_t am_chain_walk_lds(const void *kernel, std::atomic<bool> (&done
 
 // step 1 (independent of where the scan starts): successor array + per-block exits
 hipError_t am_launch_chain_prepare(const uint32_t *pos, const uint32_t *tgt, uint32_t M, uint32_t *jump0,
-                                   uint32_t *scratch, int want_last, hipStream_t s, const uint32_t *Mp, int have_succ)
+                                   uint32_t *scratch, int want_last, hipStream_t s, const uint32_t *Mp, int have_succ,
+                                   uint32_t *scalars)
 {
     if (M == 0) return hipSuccess;
     const am_chain_layout L = am_chain_layout_of(M);
     if (!have_succ)                                           // (am_k_cand already wrote the successors)
     hipLaunchKernelGGL(am_k_chain_succ, dim3(am_grid((uint64_t)M + 1, 256)), dim3(256), 0, s, pos, tgt, M, jump0, Mp);
     hipLaunchKernelGGL(am_k_cblk_exit, dim3(L.nblk), dim3(AM_CB_THREADS), 0, s, jump0, M, L.headw, scratch,
-                       want_last ? scratch + L.off_last : nullptr, reinterpret_cast<uint16_t *>(scratch + L.off_head), Mp);
+                       want_last ? scratch + L.off_last : nullptr, reinterpret_cast<uint16_t *>(scratch + L.off_head), Mp, scalars);
     return hipGetLastError();
 }
 
 // steps 2 + 3: which candidates the scan that starts at position cur0 visits, and what it does with them:
-// emit_idx[0 .. *n_out) = the hits in position order, scalars[0] = resume position
+// emit_idx[0 .. *n_out) = the hits in position order, scalars[0] = resume position.
+// Two forms.  FUSED (am_k_cblk_visit, one launch): for a plain scan -- the start position comes from the host, nobody waits for
+// the walk alone, am_launch_chain_prepare cleared scalars[0 .. 1], the host waits for this scan before it enqueues another
+// (entry_slots != null says all that: one {epoch, entry} word per block, zero at allocation) -- whose nblk + 1 workgroups of 1024 threads are resident in one round (one per CU).  SEPARATE
+// (am_k_cblk_walk, then am_k_cblk_mark): everything else.  walk_mode (test builds): AM_WALK_SEPARATE / AM_WALK_FUSED force
+// either form where both are legal, the CU count notwithstanding.  *fused_out: which one ran.
 hipError_t am_launch_chain_visit(const uint32_t *pos, const uint32_t *jump0, uint32_t M, uint32_t cur0,
                                  uint32_t *scratch, const uint8_t *valid, const uint32_t *e, const uint32_t *tgt,
                                  uint32_t emit_max, uint32_t own_lo, uint32_t own_hi, uint4 *emit_idx, uint32_t *n_out,
                                  unsigned long long *slots, uint32_t epoch, uint32_t *ticket, uint32_t *ticket_base,
                                  uint32_t *scalars, int want_resume, hipStream_t s, const uint32_t *Mp, const am_entry_src *entry_src,
-                                 const float *inavg, hipEvent_t after_walk)
+                                 const float *inavg, hipEvent_t after_walk, unsigned long long *entry_slots, int walk_mode,
+                                 int *fused_out)
 {
+    if (fused_out) *fused_out = 0;
     if (M == 0) return hipSuccess;
     const am_chain_layout L = am_chain_layout_of(M);
-    static std::atomic<bool> attr_set[64];
-    if (hipError_t rc = am_chain_walk_lds(reinterpret_cast<const void *>(&am_k_cblk_walk), attr_set); rc != hipSuccess)
-        return rc;
     const size_t lds = am_chain_walk_lds_bytes(L.nblk, L.headw);
     if (lds > AM_CB_WALK_LDS) return hipErrorInvalidValue;   // (more than ~75 000 blocks of 2048 candidates in one scan)
-    am_entry_src es;
-    if (entry_src) es = *entry_src;
-    else { es.msgs = nullptr; es.world = 0; es.rank = 0; es.cap = 0; es.base_abs = 0; es.flags = nullptr; es.exit_out = nullptr; es.cur_in = nullptr; }
-    hipLaunchKernelGGL(am_k_cblk_walk, dim3(1), dim3(1024), lds, s, pos, scratch, reinterpret_cast<const uint16_t *>(scratch + L.off_head), M, L.nblk,
-                       L.headw, cur0, scratch + L.off_entry, scalars, Mp, es);
     am_emit_args ea;
     ea.valid = valid; ea.pos = pos; ea.e = e; ea.tgt = tgt; ea.inavg = inavg; ea.emit_max = emit_max; ea.own_lo = own_lo;
     ea.own_hi = own_hi; ea.emit_idx = emit_idx; ea.n_out = n_out; ea.slots = slots; ea.epoch = epoch; ea.scalars = scalars;
     ea.want_resume = want_resume;
     ea.ticket = ticket; ea.ticket_base = *ticket_base;
+    bool fused = entry_slots && !entry_src && !after_walk && walk_mode != AM_WALK_SEPARATE;
+#if !defined(AM_HIP_EMULATION)                                // (the emulation runs one workgroup after the other: nothing to be resident)
+    if (fused && walk_mode != AM_WALK_FUSED) fused = L.nblk + 1u <= (uint32_t)am_device_cus();
+#endif
+    if (fused) {
+        static std::atomic<bool> attr_set[64];
+        if (hipError_t rc = am_chain_walk_lds(reinterpret_cast<const void *>(&am_k_cblk_visit), attr_set); rc != hipSuccess)
+            return rc;
+        const size_t vlds = ((lds > AM_CB_MARK_LDS ? lds : AM_CB_MARK_LDS) + 15) & ~(size_t)15;
+        hipLaunchKernelGGL(am_k_cblk_visit, dim3(L.nblk + 1u), dim3(AM_CB_VTHREADS), vlds, s, pos, scratch,
+                           reinterpret_cast<const uint16_t *>(scratch + L.off_head), jump0, M, L.nblk, L.headw, cur0,
+                           scratch + L.off_entry, entry_slots, ea, Mp);
+        const hipError_t rc = hipGetLastError();
+        if (rc == hipSuccess) { *ticket_base += L.nblk + 1u; if (fused_out) *fused_out = 1; }   // (every workgroup of a launch that happened draws one)
+        return rc;
+    }
+    static std::atomic<bool> attr_set[64];
+    if (hipError_t rc = am_chain_walk_lds(reinterpret_cast<const void *>(&am_k_cblk_walk), attr_set); rc != hipSuccess)
+        return rc;
+    am_entry_src es;
+    if (entry_src) es = *entry_src;
+    else { es.msgs = nullptr; es.world = 0; es.rank = 0; es.cap = 0; es.base_abs = 0; es.flags = nullptr; es.exit_out = nullptr; es.cur_in = nullptr; }
+    hipLaunchKernelGGL(am_k_cblk_walk, dim3(1), dim3(1024), lds, s, pos, scratch, reinterpret_cast<const uint16_t *>(scratch + L.off_head), M, L.nblk,
+                       L.headw, cur0, scratch + L.off_entry, scalars, Mp, es);
     if (hipError_t rc = hipGetLastError(); rc != hipSuccess) return rc;   // (the walk's launch)
     // (am_spipe: the walk has written where the scan leaves this chunk -- all the next chunk's resolve step waits for)
     if (after_walk) if (hipError_t rc = hipEventRecord(after_walk, s); rc != hipSuccess) return rc;

@@ -175,6 +175,11 @@ class Library(object):
         for name in ("am_get_address_gate", "am_pipe_get_address_gate"):
             getattr(L, name).argtypes = [vp, C.POINTER(ci), C.POINTER(f64)]
         L.am_get_address_gate_stats.argtypes = [vp, pu64, pu64, pu64, pu64]
+        for name in ("am_set_address_repair", "am_pipe_set_address_repair"):
+            getattr(L, name).argtypes = [vp, ci]
+        for name in ("am_get_address_repair", "am_pipe_get_address_repair"):
+            getattr(L, name).argtypes = [vp]
+        L.am_get_address_repair_stats.argtypes = [vp, pu64, pu64]
         self.L = L
         if L.am_abi_version() != ABI_VERSION:
             raise OSError("ABI version mismatch in %s" % path)
@@ -309,6 +314,21 @@ class Context(object):
         self._chk(self.lib.L.am_get_address_gate_stats(self._h, p[0], p[1], p[2], p[3] if not_learned else None))
         names = ("taught", "passed", "dropped", "not_learned")[:4 if not_learned else 3]
         return dict(zip(names, (int(x.value) for x in v)))
+
+    def set_address_repair(self, max_bits):
+        """Opt-in repair behind the address gate (am_set_address_repair; 0 = off, 1): an address/parity reply the gate drops is
+        kept if flipping exactly one of its bits 5.. makes its syndrome an address that is alive; it comes out with that bit
+        flipped, crc = the address and reserved[1] = 1.  Inert while the gate is off."""
+        self._chk(self.lib.L.am_set_address_repair(self._h, int(max_bits)))
+
+    def get_address_repair(self):
+        return int(self.lib.L.am_get_address_repair(self._h))
+
+    def address_repair_stats(self):
+        """Since the context was created: dict(repaired=, ambiguous=) (am_get_address_repair_stats)."""
+        v = [C.c_uint64(0), C.c_uint64(0)]
+        self._chk(self.lib.L.am_get_address_repair_stats(self._h, C.byref(v[0]), C.byref(v[1])))
+        return dict(repaired=int(v[0].value), ambiguous=int(v[1].value))
 
     def reset(self):
         self._chk(self.lib.L.am_reset(self._h))
@@ -728,6 +748,13 @@ class Pipe(object):
         mode, ttl = C.c_int(0), C.c_double(0.0)
         self._chk(self.lib.L.am_pipe_get_address_gate(self._h, C.byref(mode), C.byref(ttl)))
         return int(mode.value), float(ttl.value)
+
+    def set_address_repair(self, max_bits):
+        """As Context.set_address_repair, for every context of the pipe; with no batch in flight."""
+        self._chk(self.lib.L.am_pipe_set_address_repair(self._h, int(max_bits)))
+
+    def get_address_repair(self):
+        return int(self.lib.L.am_pipe_get_address_repair(self._h))
 
     def submit(self, iq):
         """A batch in host memory.  The samples must stay valid until the batch is collected: the (possibly converted)

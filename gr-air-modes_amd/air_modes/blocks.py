@@ -60,13 +60,16 @@ class slicer(object):
     """air_modes.slicer(queue): PPM bit slicer + framer + CRC; posts one text message per
     accepted reply to `queue` (lib/slicer_impl.cc:186-194)."""
 
-    def __init__(self, queue, device=-1, lib=None, _ctx=None, fix_errors=0, address_gate=0, address_ttl=60.0):
+    def __init__(self, queue, device=-1, lib=None, _ctx=None, fix_errors=0, address_gate=0, address_ttl=60.0,
+                 address_repair=0):
         self._queue = queue
         self._ctx = _ctx or _capi.Context(4e6, 7.0, use_pmf=True, device=device, lib=lib)
         if fix_errors:                # repair instead of the drop at slicer_impl.cc:179-182 (am_set_fix_errors)
             self._ctx.set_fix_errors(fix_errors)
         if address_gate:              # address/parity replies need a taught address (am_set_address_gate; :170-182 checks none)
             self._ctx.set_address_gate(address_gate, address_ttl)
+        if address_repair:            # ... and one wrong bit of a reply the gate drops is looked for (am_set_address_repair)
+            self._ctx.set_address_repair(address_repair)
         self._first = True          # the member ostringstream's precision quirk, slicer_impl.h:43
 
     def post(self, packets):

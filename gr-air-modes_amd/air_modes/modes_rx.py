@@ -1,7 +1,7 @@
 """File-source subset of the reference's command-line receiver (apps/modes_rx:32-110,
 python/radio.py:90-118,221-234):
 
-    python -m air_modes.modes_rx -s capture.cf32 -r 2e6 [-T 7.0] [--no-pmf] [--fix-errors N] [--address-gate M] [--address-ttl S] [-l lat,lon] [-n] [--raw]
+    python -m air_modes.modes_rx -s capture.cf32 -r 2e6 [-T 7.0] [--no-pmf] [--fix-errors N] [--address-gate M] [--address-ttl S] [--address-repair N] [-l lat,lon] [-n] [--raw]
     python -m air_modes.modes_rx -s rtlsdr.cu8 -r 2.4e6            (-f cu8 when the name does not say it)
 
 Reads a gr_complex file (interleaved little-endian float32 I,Q -- what
@@ -52,6 +52,9 @@ def build_parser():
                     "[default=%(default)s]")
     ap.add_argument("--address-ttl", type=float, default=60.0, metavar="SECONDS",
                     help="how long a heard address is believed [default=%(default)s]")
+    ap.add_argument("--address-repair", type=int, choices=[0, 1], default=0,
+                    help="with --address-gate: keep a reply the gate drops if flipping exactly one of its bits gives it the "
+                    "address of an aircraft heard within --address-ttl [default=%(default)s]")
     ap.add_argument("-l", "--location", default=None, help="receiver position as lat,lon (enables range/bearing "
                     "and surface positions)")                                                            # modes_rx:40
     ap.add_argument("-n", "--no-print", action="store_true", help="do not print decoded reports")       # modes_rx:45
@@ -83,7 +86,8 @@ def main(argv=None, out=None):
         # on the GPU, bit-identical to resample.arb_resampler (its definition); the output stays on the device
         rx_rate, resampler = 4e6, resample.gpu_resampler(4e6 / args.rate)
     rx = rx_path(rx_rate, args.threshold, queue, use_pmf=args.pmf, use_dcblock=args.dcblock, fix_errors=args.fix_errors,
-                 address_gate=args.address_gate, address_ttl=args.address_ttl)    # (below 4 Msps: the window runs at 4 Msps too)
+                 address_gate=args.address_gate, address_ttl=args.address_ttl,
+                 address_repair=args.address_repair)    # (below 4 Msps: the window runs at 4 Msps too)
     publisher = pubsub()
     feed = make_parser(publisher)
     my_position = [float(n) for n in args.location.split(",")] if args.location else None

@@ -14,7 +14,7 @@ from .blocks import slicer as _slicer
 
 class rx_path(object):
     def __init__(self, rate, threshold, queue, use_pmf=False, use_dcblock=False, device=-1, lib=None, fix_errors=0,
-                 address_gate=0, address_ttl=60.0):
+                 address_gate=0, address_ttl=60.0, address_repair=0):
         self._rate = int(rate)
         self._threshold = threshold
         self._queue = queue
@@ -24,7 +24,7 @@ class rx_path(object):
                                   use_dcblock=use_dcblock, device=device, lib=lib)
         self._slicer = _slicer(queue, _ctx=self._ctx)
         self.packets = 0
-        self.repaired = 0             # ... of them repaired (set_fix_errors)
+        self.repaired = 0             # ... of them repaired (set_fix_errors, and set_address_repair: both leave reserved[1] != 0)
         self._gate_used = False
         self.gated = 0                # packets the address gate dropped so far (set_address_gate); they are not in `packets`
         self.samples = 0
@@ -32,6 +32,8 @@ class rx_path(object):
             self.set_fix_errors(fix_errors)
         if address_gate:
             self.set_address_gate(address_gate, address_ttl)
+        if address_repair:
+            self.set_address_repair(address_repair)
 
     # --- reference surface: python/rx_path.py:67-87 ---
     def set_rate(self, rate):
@@ -70,6 +72,15 @@ class rx_path(object):
 
     def get_address_gate(self):
         return self._ctx.get_address_gate()
+
+    def set_address_repair(self, max_bits):
+        """From the next work() on, keep an address/parity reply the gate drops if flipping exactly one of its bits gives it the
+        address of an aircraft that is alive (am_set_address_repair; 0 = off, 1).  Inert while the gate is off.  `repaired`
+        counts these packets too: it counts reserved[1] != 0."""
+        self._ctx.set_address_repair(max_bits)
+
+    def get_address_repair(self):
+        return self._ctx.get_address_repair()
 
     # --- what the scheduler does for the reference: push samples through ---
     def set_rx_time(self, offset, secs, frac):
@@ -122,12 +133,14 @@ class rx_path_bank(object):
     of WHOLE streams (item counts and time stamps start at 0): the batch form of rx_path.work(capture, flush=True)."""
 
     def __init__(self, rate, threshold, queues, use_pmf=False, device=-1, lib=None, fix_errors=0, address_gate=0,
-                 address_ttl=60.0):
+                 address_ttl=60.0, address_repair=0):
         self._ctx = _capi.Context(float(int(rate)), float(threshold), use_pmf=use_pmf, device=device, lib=lib)
         if fix_errors:
             self._ctx.set_fix_errors(fix_errors)
         if address_gate:              # every receiver's capture is a stream of its own: a map per receiver
             self._ctx.set_address_gate(address_gate, address_ttl)
+        if address_repair:            # receiver j's replies are searched in receiver j's map only
+            self._ctx.set_address_repair(address_repair)
         self._slicers = [_slicer(q, _ctx=self._ctx) for q in queues]
         self.packets = [0] * len(queues)
 
@@ -140,6 +153,10 @@ class rx_path_bank(object):
     def work_device(self, dev_ptr, lengths):
         """The same with the packed buffer (layout: context().multi_layout(lengths), zeros between the streams) already on the GPU."""
         return self._post(self._ctx.process_multi(None, lengths, device_ptr=dev_ptr))
+
+    def set_address_repair(self, max_bits):
+        """As rx_path.set_address_repair, from the next work() on."""
+        self._ctx.set_address_repair(max_bits)
 
     def _post(self, per_stream):
         for j, pk in enumerate(per_stream):

@@ -125,6 +125,10 @@ struct am_ctx {
     bool gate_live = false;       // the scan in flight / last collected ran with the gate: pin_scalars[9..11] are its counters
     am_gate_args ga = {};         // ... and its arguments (am_k_gate_commit gets them again, with the count the host accepted)
     uint64_t gate_stat[3] = {0, 0, 0};   // taught, passed, dropped since am_create (accepted scans only)
+    // am_set_address_repair: one wrong bit of an address/parity reply the gate fails, found among the addresses alive
+    int gate_repair = 0;          // 0: off; 1: on (inert while gate_mode is 0)
+    DevBuf gate_list;             // counters and the hit indices of the failed address/parity records (am_gate_args.rl)
+    uint64_t repair_stat[2] = {0, 0};    // repaired, ambiguous since am_create (accepted scans only)
     int tile = 0;
     // Speculative launches: the candidate count of a scan is only known on the device when its kernels
     // are enqueued.  Instead of a host round trip in the middle of the pipeline, the streaming path
@@ -320,7 +324,7 @@ int ensure_shard_exit(am_ctx *c)
 }
 
 // the pinned scalar block the tail kernels write into: [0..2] results of the slice launch, [3..4] time shards, [5] chained-scan
-// error, [8] completion ticket, [9..11] address gate, [12..13] a time chunk's exit word
+// error, [8] completion ticket, [9..11] address gate, [12..13] a time chunk's exit word, [14..15] the gate's repair
 int ensure_pin_scalars(am_ctx *c)
 {
     if (c->pin_scalars) return AM_OK;
@@ -767,6 +771,11 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
     a.t_mask = AM_GATE_MAP_SLOTS - 1u;
     a.t_limit = (unsigned long long)AM_GATE_MAP_SLOTS / 4 * 3;
     a.packets = packets;
+    if (c->gate_repair) {
+        ENSURE(c, c->gate_list, ((size_t)AM_GATE_RL_HDR + (n_max ? n_max : 1)) * sizeof(uint32_t));
+        a.rl = (uint32_t *)c->gate_list.p;
+        a.crc_pow = (const uint32_t *)c->crc_pow.p;
+    }
     const size_t K = c->multi_off.size();
     if (K) {
         // the host sorts the packets into streams only after the scan (sort_into_streams): the gate runs before that and needs the
@@ -835,7 +844,11 @@ int chain_collect(am_ctx *c, const TailReq &req, uint32_t n_max, uint32_t *final
     if (n_emit > n_max) return fail(c, AM_EHIP, "internal: more hits than the spacing bound allows");
     c->n_hits = n_emit;
     if (c->gate_live)                                        // (an accepted scan: a repeated one returned above)
+    {
         for (int k = 0; k < 3; k++) c->gate_stat[k] += c->pin_scalars[9 + k];
+        if (c->ga.rl)
+            for (int k = 0; k < 2; k++) c->repair_stat[k] += c->pin_scalars[14 + k];
+    }
     if (!req.keep_bursts) {
         const double TC = am_now_us();
         for (uint32_t i = 0; i < n_emit; i++) {
@@ -939,7 +952,7 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
                                              (uint32_t)c->tt.size(), keep_dev ? (float *)c->bursts.p : nullptr,
                                              keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p,
                                              c->pin_packets, (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp,
-                                             c->fix_bits, gate ? 1 : 0));
+                                             c->fix_bits, gate ? (c->ga.rl ? 2 : 1) : 0));
     else
     HIPCHK(c, am_launch_extract_slice(sc.ref.bb, (const float *)c->inavg.p, c->spc, c->frac ? (const int *)c->chip_idx.p : nullptr,
                                       c->geom.hist0, (const uint4 *)c->emit_idx.p, n_ptr, n_max,
@@ -947,7 +960,7 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
                                       (const am_time_tag *)c->tt_dev.p, (uint32_t)c->tt.size(),
                                       keep_dev ? (float *)c->bursts.p : nullptr,
                                       keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p, c->pin_packets,
-                                      (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp, c->fix_bits, gate ? 1 : 0));
+                                      (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp, c->fix_bits, gate ? (c->ga.rl ? 2 : 1) : 0));
     if (gate) HIPCHK(c, am_launch_gate(c->ga, n_max, c->stream));     // behind the slicing launch, in front of the ticket
     if (req.copy_tail)
         // time shards: the samples the next step needs in front of its chunk, kept while this step's are still in place
@@ -955,7 +968,7 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
         HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
     const uint32_t seq = ++c->ticket_seq;
     if (gate)
-        HIPCHK(c, am_launch_gate_ticket(c->pin_scalars + 8, seq, c->ga.cnt, c->pin_scalars + 9, c->stream));
+        HIPCHK(c, am_launch_gate_ticket(c->pin_scalars + 8, seq, c->ga.cnt, c->ga.rl, c->pin_scalars + 9, c->stream));
     else
     HIPCHK(c, am_launch_ticket(c->pin_scalars + 8, seq, c->stream, req.flag_src, req.flag_src ? c->pin_scalars + 4 : nullptr,
                                req.word_src, req.word_src ? reinterpret_cast<uint64_t *>(c->pin_scalars + 12) : nullptr));
@@ -1222,7 +1235,7 @@ void am_destroy(am_ctx *c)
                      &c->pos, &c->e, &c->tgt, &c->valid, &c->jump, &c->emit_idx,
                      &c->lb_dc, &c->lb_mark, &c->lb_entry, &c->cblk_cnt, &c->cblk_off, &c->scalars, &c->bursts, &c->tags, &c->packets, &c->crc_pow,
                      &c->recs, &c->cscratch, &c->dc_m1, &c->dc_y, &c->tt_dev, &c->wgmax, &c->shard_exit, &c->chip_idx,
-                     &c->gate_rec, &c->gate_scratch, &c->gate_map, &c->gate_multi};
+                     &c->gate_rec, &c->gate_scratch, &c->gate_map, &c->gate_multi, &c->gate_list};
     for (DevBuf *b : all) release(*b);
     if (c->pin_packets) (void)hipHostFree(c->pin_packets);
     if (c->pin_tags) (void)hipHostFree(c->pin_tags);
@@ -1365,6 +1378,24 @@ int am_get_address_gate_stats(const am_ctx *c, uint64_t *taught, uint64_t *passe
         }
         *not_learned = v;
     }
+    return AM_OK;
+}
+
+// The gate drops "a real reply with one wrong bit", which reads as a reply of another aircraft; with this on, such a reply is
+// searched for the one bit whose flip gives it the address of an aircraft that is alive (am_k_gate_repair).  From the next scan on.
+int am_set_address_repair(am_ctx *c, int max_bits)
+{
+    if (!c) return AM_EINVAL;
+    if (max_bits < 0 || max_bits > 1) return fail(c, AM_EINVAL, "address_repair: max_bits must be 0 or 1");
+    c->gate_repair = max_bits;
+    return AM_OK;
+}
+int am_get_address_repair(const am_ctx *c) { return c ? c->gate_repair : AM_EINVAL; }
+int am_get_address_repair_stats(const am_ctx *c, uint64_t *repaired, uint64_t *ambiguous)
+{
+    if (!c) return AM_EINVAL;
+    if (repaired) *repaired = c->repair_stat[0];
+    if (ambiguous) *ambiguous = c->repair_stat[1];
     return AM_OK;
 }
 
@@ -1973,19 +2004,22 @@ int am_slicer_work(am_ctx *c, const float *bursts, const am_tag *tags, uint64_t 
         if (int rc = gate_prepare(c, nb32, nullptr, (am_packet *)c->packets.p); rc != AM_OK) return rc;
     HIPCHK(c, am_launch_slice((float *)c->bursts.p, (am_tag *)c->tags.p, (const uint32_t *)c->scalars.p, nb32,
                               (uint32_t *)c->crc_pow.p, (am_packet *)c->packets.p, (const uint32_t *)c->scalars.p, nullptr,
-                              c->stream, nullptr, c->fix_bits, gate ? 1 : 0));
+                              c->stream, nullptr, c->fix_bits, gate ? (c->ga.rl ? 2 : 1) : 0));
     unsigned long long gcnt[3] = {0, 0, 0};
+    uint32_t rcnt[2] = {0, 0};
     if (gate) {
         c->ga.K = 0;                                          // (a layout left by am_submit_multi is not this call's)
         HIPCHK(c, am_launch_gate(c->ga, nb32, c->stream));
         if (int rc = gate_commit(c, nb32); rc != AM_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(gcnt, c->ga.cnt, sizeof(gcnt), hipMemcpyDeviceToHost, c->stream));
+        if (c->ga.rl) HIPCHK(c, hipMemcpyAsync(rcnt, c->ga.rl + 1, sizeof(rcnt), hipMemcpyDeviceToHost, c->stream));
     }
     c->h_packets.resize(nb);
     HIPCHK(c, hipMemcpyAsync(c->h_packets.data(), c->packets.p, nb * sizeof(am_packet), hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < 3; k++) c->gate_stat[k] += gcnt[k];
+    for (int k = 0; k < 2; k++) c->repair_stat[k] += rcnt[k];
     c->pending.clear();
     collect_accepted(c);
     return hand_out(c, out, cap, n_out);
@@ -2835,6 +2869,20 @@ int am_pipe_get_address_gate(const am_pipe *p, int *mode, double *ttl_seconds)
     if (!p || p->sub.empty()) return AM_EINVAL;
     return am_get_address_gate(p->sub[0], mode, ttl_seconds);
 }
+
+int am_pipe_set_address_repair(am_pipe *p, int max_bits)
+{
+    if (!p) return AM_EINVAL;
+    if (max_bits < 0 || max_bits > 1 || p->inflight) {
+        p->last_fail = nullptr;
+        snprintf(p->err, sizeof(p->err), "%s", p->inflight ? "address_repair: collect the batches in flight first"
+                                                           : "address_repair: max_bits must be 0 or 1");
+        return AM_EINVAL;
+    }
+    for (am_ctx *c : p->sub) c->gate_repair = max_bits;
+    return AM_OK;
+}
+int am_pipe_get_address_repair(const am_pipe *p) { return p && !p->sub.empty() ? p->sub[0]->gate_repair : AM_EINVAL; }
 
 int am_pipe_submit(am_pipe *p, const float *iq, uint64_t n, uint32_t flags)
 {

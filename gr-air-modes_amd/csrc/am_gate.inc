@@ -16,7 +16,10 @@
 //                     or the context's map, taught by EARLIER calls, has it with s - last <= ttl;
 //                     what fails, and with mode 2 every reserved format, loses packets[i].reserved[0] (a byte store to pinned
 //                     memory, as the slicer's own reject)
-//   am_k_gate_ticket  am_k_ticket + the call's three counters for the host
+//   am_k_gate_repair  only with am_set_address_repair: every address/parity reply the test failed is searched for the one bit whose
+//                     flip makes its syndrome an address that is alive (the same three-way lookup); exactly one: the packet is
+//                     rewritten and kept, and moves from the dropped counter to the repaired one
+//   am_k_gate_ticket  am_k_ticket + the call's three counters for the host (am_k_gate_repair_ticket: five)
 //
 // and, only once the host has ACCEPTED the scan (a speculative scan that is repeated, or one that timed out, never gets here):
 //
@@ -111,6 +114,32 @@ __global__ void __launch_bounds__(256) am_k_gate_teach(am_gate_args a)
     if ((threadIdx.x & (AM_WAVE - 1)) == 0 && m) atomicAdd(&a.cnt[0], (unsigned long long)__popcll(m));
 }
 
+// Is address addr alive for stream j at item count s (window w = s / ttl)?  The three ways of the header: the call's table in
+// window w, the call's table in window w - 1, the context's map.  The gate's own test and the repair's search ask here.
+__device__ __forceinline__ bool am_gate_alive(const am_gate_args &a, uint32_t j, uint32_t addr, unsigned long long s)
+{
+    const unsigned long long w = s / a.ttl;
+    uint32_t h = am_gate_slot(a, j, addr, w, 0u);
+    if (h != ~0u && ~a.s_first[h] < s) return true;
+    if (w > 0ull) {
+        h = am_gate_slot(a, j, addr, w - 1ull, 0u);
+        if (h != ~0u && s - (a.s_last[h] - 1ull) <= a.ttl) return true;
+    }
+    uint32_t t = (uint32_t)am_gate_mix(addr) & a.t_mask;     // the context's map: what earlier calls of this stream taught
+    for (uint32_t probe = 0; probe <= a.t_mask; ++probe, t = (t + 1) & a.t_mask) {
+        const unsigned long long k = a.t_key[t];
+        if (k == 0ull) break;
+        if (k == (unsigned long long)addr + 1ull) {
+            const unsigned long long l = a.t_last[t];
+            return l != 0ull && l - 1ull <= s && s - (l - 1ull) <= a.ttl;
+        }
+    }
+    return false;
+}
+
+// REPAIR: 1 = the hit index of every address/parity record that fails goes onto the repair's list (am_k_gate_repair below; in any
+// order: each entry is looked at on its own); 0 is the test alone.
+template <int REPAIR>
 __global__ void __launch_bounds__(256) am_k_gate_test(am_gate_args a)
 {
     const uint32_t n = a.n_ptr ? *a.n_ptr : a.n;
@@ -125,26 +154,10 @@ __global__ void __launch_bounds__(256) am_k_gate_test(am_gate_args a)
             if (r.cls == AM_GC_OTHER) {
                 keep = a.mode != 2;
             } else {
-                const unsigned long long w = s / a.ttl;
-                uint32_t h = am_gate_slot(a, j, r.addr, w, 0u);
-                keep = h != ~0u && ~a.s_first[h] < s;
-                if (!keep && w > 0ull) {
-                    h = am_gate_slot(a, j, r.addr, w - 1ull, 0u);
-                    keep = h != ~0u && s - (a.s_last[h] - 1ull) <= a.ttl;
-                }
-                if (!keep) {                                 // the context's map: what earlier calls of this stream taught
-                    uint32_t t = (uint32_t)am_gate_mix(r.addr) & a.t_mask;
-                    for (uint32_t probe = 0; probe <= a.t_mask; ++probe, t = (t + 1) & a.t_mask) {
-                        const unsigned long long k = a.t_key[t];
-                        if (k == 0ull) break;
-                        if (k == (unsigned long long)r.addr + 1ull) {
-                            const unsigned long long l = a.t_last[t];
-                            keep = l != 0ull && l - 1ull <= s && s - (l - 1ull) <= a.ttl;
-                            break;
-                        }
-                    }
-                }
+                keep = am_gate_alive(a, j, r.addr & 0xFFFFFFu, s);
                 passed = keep;
+                if constexpr (REPAIR > 0)
+                    if (!keep) a.rl[AM_GATE_RL_HDR + atomicAdd(&a.rl[0], 1u)] = i;     // (at most n entries: one per record)
             }
             if (!keep) {
                 a.packets[i].reserved[0] = 0;
@@ -156,6 +169,45 @@ __global__ void __launch_bounds__(256) am_k_gate_test(am_gate_args a)
     if ((threadIdx.x & (AM_WAVE - 1)) == 0) {
         if (mp) atomicAdd(&a.cnt[1], (unsigned long long)__popcll(mp));
         if (md) atomicAdd(&a.cnt[2], (unsigned long long)__popcll(md));
+    }
+}
+
+// Repair of an address/parity reply with one wrong bit (am_set_address_repair; DESIGN.md 15).  The syndrome of such a reply is
+// address ^ syn(j) when bit j is wrong, so crc ^ syn(j) is tried for every j = 5 .. nbits - 1 against the addresses that are alive
+// where the reply stands; exactly one hit: the reply is that aircraft's with bit j flipped.  One wave per list entry, entries
+// wave-strided over a fixed grid; lane l owns bits l and l + 64, as in am_slice_wave.  The record (am_slice_wave<FIX, 2>) carries
+// the DF above the syndrome: DF16/20/21 are long.  Lane 0 of a wave that repairs reads the one data byte back from the packet
+// array, which the slicing wave wrote in full (the packet was "ok" there); nothing else is ever read from it.
+__global__ void __launch_bounds__(256) am_k_gate_repair(am_gate_args a)
+{
+    const int lane = threadIdx.x & (AM_WAVE - 1);
+    const uint32_t nw = gridDim.x * (blockDim.x / AM_WAVE);
+    const uint32_t n = a.rl[0];
+    for (uint32_t k = blockIdx.x * (blockDim.x / AM_WAVE) + threadIdx.x / AM_WAVE; k < n; k += nw) {      // (wave-uniform)
+        const uint32_t i = a.rl[AM_GATE_RL_HDR + k];
+        const am_gate_rec r = a.rec[i];
+        uint32_t j;
+        unsigned long long s;
+        (void)am_gate_locate(a, r.sample, j, s);             // (it is on the list: am_k_gate_test located it)
+        const uint32_t crc = r.addr & 0xFFFFFFu;
+        const int nbits = (r.addr >> 24) & 16u ? 112 : 56;
+        const bool h0 = lane >= 5 && lane < nbits && am_gate_alive(a, j, crc ^ a.crc_pow[nbits - 1 - lane], s);
+        const bool h1 = lane + 64 < nbits && am_gate_alive(a, j, crc ^ a.crc_pow[nbits - 1 - (lane + 64)], s);
+        const unsigned long long f0 = __ballot(h0), f1 = __ballot(h1);
+        const int hits = __popcll(f0) + __popcll(f1);
+        if (lane != 0 || hits == 0) continue;
+        if (hits > 1) {
+            atomicAdd(&a.rl[2], 1u);
+            continue;
+        }
+        const int b = f0 ? __ffsll((long long)f0) - 1 : 63 + __ffsll((long long)f1);
+        am_packet *p = a.packets + i;
+        p->data[b >> 3] = (uint8_t)(p->data[b >> 3] ^ (0x80u >> (b & 7)));
+        p->crc = crc ^ a.crc_pow[nbits - 1 - b];
+        p->reserved[1] = 1;
+        p->reserved[0] = 1;
+        atomicAdd(&a.cnt[2], ~0ull);                         // no longer dropped ...
+        atomicAdd(&a.rl[1], 1u);                             // ... but repaired
     }
 }
 
@@ -198,6 +250,18 @@ __global__ void am_k_gate_ticket(uint32_t *host_word, uint32_t seq, const unsign
     __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ... and with the repair on, two more: repaired, ambiguous (cnt_dst[5], [6])
+__global__ void am_k_gate_repair_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl,
+                                        uint32_t *cnt_dst)
+{
+    cnt_dst[0] = (uint32_t)cnt[0];
+    cnt_dst[1] = (uint32_t)cnt[1];
+    cnt_dst[2] = (uint32_t)cnt[2];
+    cnt_dst[5] = rl[1];
+    cnt_dst[6] = rl[2];
+    __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 size_t am_gate_scratch_bytes(uint32_t slots) { return ((size_t)4 + (size_t)3 * slots) * sizeof(unsigned long long); }
 
 void am_gate_scratch_layout(am_gate_args &a, void *scratch, uint32_t slots)
@@ -213,9 +277,17 @@ void am_gate_scratch_layout(am_gate_args &a, void *scratch, uint32_t slots)
 hipError_t am_launch_gate(const am_gate_args &a, uint32_t n_max, hipStream_t s)
 {
     hipError_t rc = hipMemsetAsync(a.cnt, 0, am_gate_scratch_bytes(a.s_mask + 1u), s);
+    if (rc == hipSuccess && a.rl) rc = hipMemsetAsync(a.rl, 0, AM_GATE_RL_HDR * sizeof(uint32_t), s);     // (the ticket reads them)
     if (rc != hipSuccess || n_max == 0) return rc;
     hipLaunchKernelGGL(am_k_gate_teach, dim3(am_grid(n_max, 256)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(am_k_gate_test, dim3(am_grid(n_max, 256)), dim3(256), 0, s, a);
+    if (!a.rl) {
+        hipLaunchKernelGGL(am_k_gate_test<0>, dim3(am_grid(n_max, 256)), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(am_k_gate_test<1>, dim3(am_grid(n_max, 256)), dim3(256), 0, s, a);
+    // a fixed, modest grid: a scan fails some hundreds of address/parity replies, and each costs one wave a few probes per lane
+    const uint32_t waves = n_max < 256u ? n_max : 256u;
+    hipLaunchKernelGGL(am_k_gate_repair, dim3(am_grid(waves, 4)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -226,8 +298,10 @@ hipError_t am_launch_gate_commit(const am_gate_args &a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t am_launch_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, uint32_t *cnt_dst, hipStream_t s)
+hipError_t am_launch_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl,
+                                 uint32_t *cnt_dst, hipStream_t s)
 {
-    hipLaunchKernelGGL(am_k_gate_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, cnt_dst);
+    if (rl) hipLaunchKernelGGL(am_k_gate_repair_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, rl, cnt_dst);
+    else hipLaunchKernelGGL(am_k_gate_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, cnt_dst);
     return hipGetLastError();
 }

@@ -298,7 +298,7 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
  * array is pinned host memory, which a kernel does not read back. */
 struct am_gate_rec {
     unsigned long long sample;   /* am_packet.sample (for K streams: still in the coordinates of the scanned buffer)          */
-    uint32_t addr;               /* teach: data[1..3], big-endian; test: the syndrome                                         */
+    uint32_t addr;               /* teach: data[1..3], big-endian; test: the syndrome (<FIX, 2>: and the DF in bits 24..28)   */
     uint32_t cls;                /* AM_GC_*                                                                                   */
 };
 #define AM_GC_NONE 0u    /* rejected by the slicer, or kept without a part in the gate (a repaired DF11 / DF17 reply)          */
@@ -325,20 +325,26 @@ struct am_gate_args {
     uint32_t t_mask;
     unsigned long long t_limit;
     am_packet *packets;
+    uint32_t *rl;                        /* am_set_address_repair: [0] entries [1] repaired [2] ambiguous, from [AM_GATE_RL_HDR]  */
+    const uint32_t *crc_pow;             /* the hit indices of the failed address/parity records; null: no repair                 */
 };
+#define AM_GATE_RL_HDR 4u
 size_t am_gate_scratch_bytes(uint32_t slots);                                   /* slots: a power of two                      */
 void am_gate_scratch_layout(am_gate_args &a, void *scratch, uint32_t slots);
 hipError_t am_launch_gate(const am_gate_args &a, uint32_t n_max, hipStream_t s);   /* zero the call's table, teach, test     */
+                                                                                   /* (a.rl: and repair)                      */
 hipError_t am_launch_gate_commit(const am_gate_args &a, hipStream_t s);            /* a.n records of an ACCEPTED scan         */
-hipError_t am_launch_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, uint32_t *cnt_dst,
-                                 hipStream_t s);
+/* cnt_dst[0..2] = taught, passed, dropped; rl (a.rl, or null): cnt_dst[5..6] = repaired, ambiguous */
+hipError_t am_launch_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl,
+                                 uint32_t *cnt_dst, hipStream_t s);
 
 /* packets[i].reserved[0] = 1 when the reference would post the message, else 0.
  * fix_bits (all three launches; no default: a caller that forgot it would run without the repair and nobody would notice):
  * which instantiation am_k_*<FIX> runs -- 0 = the kernels as they are without the repair; 1, 2 = DF11 / DF17 replies with up to
  * that many wrong bits are repaired (am_set_fix_errors) and the number flipped is left in reserved[1].
  * gate (likewise): 1 = am_k_*<FIX, 1>, which also leaves an am_gate_rec per hit at the address in scalars[AM_GATE_REC_WORD]
- * (scalars must not be null then); 0 = the kernels as they are without the gate */
+ * (scalars must not be null then); 2 = am_k_*<FIX, 2>: the same, and an address/parity record carries its DF (am_k_gate_repair);
+ * 0 = the kernels as they are without the gate */
 hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const uint32_t *n_ptr, uint32_t n_max,
                            const uint32_t *crc_pow, am_packet *packets, const uint32_t *scalars,
                            uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits, int gate);

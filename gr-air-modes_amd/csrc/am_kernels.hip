@@ -2299,7 +2299,8 @@ __device__ __forceinline__ int am_fix_errors(unsigned long long &m0, unsigned lo
 // FIX: wrong bits to repair (am_fix_errors above): 1 or 2; 0 is the code as it was before the repair existed.
 // GATE: 1 = lane 0 also files the hit's part in the address gate (am_gate.inc) as record i of the array whose address the
 // context keeps in scalars[AM_GATE_REC_WORD] (device memory; a kernel argument of its own would change the <FIX, 0> kernels'
-// descriptors); 0 is the code as it was before the gate existed, and never looks at scalars.
+// descriptors); 0 is the code as it was before the gate existed, and never looks at scalars.  2 (am_set_address_repair) = 1, and
+// the record of an address/parity reply carries its DF above the 24 bits of the syndrome.
 template <int FIX, int GATE>
 __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, uint32_t i, int lane,
                                               const uint32_t *__restrict__ crc_pow, am_packet *__restrict__ packets,
@@ -2372,6 +2373,7 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
                     }
                 } else if (mt == 0 || mt == 4 || mt == 5 || mt == 16 || mt == 20 || mt == 21) {
                     r.cls = AM_GC_TEST;
+                    if constexpr (GATE > 1) r.addr |= mt << 24;               // (am_k_gate_repair derives the length from it)
                 } else {
                     r.cls = AM_GC_OTHER;
                 }
@@ -2395,7 +2397,8 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
 // until am_set_fix_errors turns the repair on, and is instruction for instruction the kernel from before the repair existed:
 // profiles/fix_errors/isa_off_kernels.txt; how to make it again: README.md there.  Likewise GATE, the address gate
 // (am_set_address_gate): <FIX, 0> is instruction for instruction the kernel <FIX> from before the gate existed:
-// profiles/address_gate/isa_off_kernels.txt.)
+// profiles/address_gate/isa_off_kernels.txt.  GATE = 2 (am_set_address_repair) is a third value, not a new argument: <FIX, 0> and
+// <FIX, 1> are the parent's kernels, profiles/address_repair/isa_off_kernels.txt.)
 template <int FIX, int GATE>
 __global__ void __launch_bounds__(256)
 am_k_slice(const float *__restrict__ bursts, const am_tag *__restrict__ tags, const uint32_t *__restrict__ n_ptr,
@@ -2472,7 +2475,7 @@ hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc,
                        emit_idx, n_ptr, pos, e, base_abs, e_off, rate, tt, ntt, bursts_out, tags_out, crc_pow, packets,   \
                        scalars, host_out, Mp)
 #define AM_XS(FIX)                                                                                                        \
-    do { if (gate) AM_XS_G(FIX, 1); else AM_XS_G(FIX, 0); } while (0)
+    do { if (gate == 2) AM_XS_G(FIX, 2); else if (gate) AM_XS_G(FIX, 1); else AM_XS_G(FIX, 0); } while (0)
     if (fix_bits == 0) AM_XS(0);
     else if (fix_bits == 1) AM_XS(1);
     else AM_XS(2);
@@ -2772,7 +2775,7 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
     // workgroups of 256 threads per CU: what the instantiation's registers allow (five at 32 samples per chip, where a lane
     // holds a 34-sample window; eight at one or two samples per chip, where the kernel is a chain of memory round trips per
     // hit and more hits in flight is all that helps), asked of the runtime once per device and instantiation
-    static std::atomic<int> per_cu[64][54];                  // (9 rates x repair of 0, 1, 2 bits x address gate off, on)
+    static std::atomic<int> per_cu[64][81];                  // (9 rates x repair of 0, 1, 2 bits x address gate off, on, on with its repair)
     int dev = 0;
     (void)hipGetDevice(&dev);
     auto resident_for = [&](const void *kernel, int slot) -> uint32_t {
@@ -2793,7 +2796,7 @@ hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long 
                            packets, scalars, host_out, Mp);                                                              \
     } while (0)
 #define AM_XS_IQ_F(S, SLOT, FIX)                                                                                          \
-    do { if (gate) AM_XS_IQ_G(S, SLOT, FIX, 1); else AM_XS_IQ_G(S, SLOT, FIX, 0); } while (0)
+    do { if (gate == 2) AM_XS_IQ_G(S, SLOT, FIX, 2); else if (gate) AM_XS_IQ_G(S, SLOT, FIX, 1); else AM_XS_IQ_G(S, SLOT, FIX, 0); } while (0)
 #define AM_XS_IQ(S, SLOT)                                                                                                 \
     do {                                                                                                                  \
         if (fix_bits == 0) AM_XS_IQ_F(S, SLOT, 0);                                                                        \
@@ -2851,7 +2854,7 @@ hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const uint32
     hipLaunchKernelGGL((am_k_slice<FIX, GATE>), dim3(am_grid(n_max, 4)), dim3(256), 0, s, bursts, tags, n_ptr, crc_pow, packets, scalars, \
                        host_out, Mp)
 #define AM_SL(FIX)                                                                                                        \
-    do { if (gate) AM_SL_G(FIX, 1); else AM_SL_G(FIX, 0); } while (0)
+    do { if (gate == 2) AM_SL_G(FIX, 2); else if (gate) AM_SL_G(FIX, 1); else AM_SL_G(FIX, 0); } while (0)
     if (fix_bits == 0) AM_SL(0);
     else if (fix_bits == 1) AM_SL(1);
     else AM_SL(2);

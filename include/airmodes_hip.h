@@ -199,6 +199,36 @@ AM_API int    am_set_address_gate(am_ctx *ctx, int mode, double ttl_seconds);
 AM_API int    am_get_address_gate(const am_ctx *ctx, int *mode, double *ttl_seconds);
 AM_API int    am_get_address_gate_stats(const am_ctx *ctx, uint64_t *taught, uint64_t *passed, uint64_t *dropped,
                                         uint64_t *not_learned);
+/* ---- opt-in repair of one wrong bit in an address/parity reply, from the addresses the gate has learned ----------------
+ * Replaces: nothing in the reference, which checks no parity here (lib/slicer_impl.cc:170-182).  The gate above drops "a real
+ *           reply with one wrong bit", because it reads as a reply of another aircraft; the gate also holds what recovers it.
+ * max_bits = 0 (default): the gate as it is above -- every packet, message text and kernel launch is what it is without this call.
+ * max_bits = 1: the packets of a stream are formed and gated exactly as above.  Repair is considered only for a packet p with
+ * p.df in {0, 4, 5, 16, 20, 21} that step 2 of the gate drops, while the gate is on (mode 1 or 2).  For such a packet, with
+ * nbits = 8 * nbytes and syn(j) = x^(nbits-1-j) mod G the syndrome of a wrong bit j (the table the slicer and am_set_fix_errors
+ * use; for j in the last 24 bits it is the single bit 1 << (nbits-1-j)):
+ *   the candidates are j = 5 .. nbits-1 with A_j = p.crc ^ syn(j)   (for an address/parity reply of aircraft A with bit j
+ *   wrong the syndrome is A ^ syn(j));
+ *   A_j is live if last[A_j] exists and s - last[A_j] <= ttl_samples: the map and the window rule the gate's own test sees at p;
+ *   exactly one live j:  the packet is kept -- bit j of data flipped, crc = A_j, reserved[1] = 1, every other field as sliced;
+ *                        am_format_message makes "<repaired hex> <A_j as %06x> <level> <secs> <frac>" of it;
+ *   no live j, or more than one: the packet is dropped as above; the second case is counted as `ambiguous`.
+ * The five DF bits are never touched: format, length and the extraction shortcut stay what the slicer chose.  A repaired reply
+ * does not teach (neither does a repaired DF11 / DF17 reply).  With max_bits 0, with the gate off, and for every packet the gate
+ * keeps, nothing changes; the packets with the repair off are a subsequence of those with it on, up to the repaired ones; the
+ * result does not depend on how the stream is cut into calls (tests/aprepair_common.py restates this in numpy).  Pinned to the
+ * reference: its own slicer, given the burst with the two chips of bit j exchanged, emits the repaired packet with crc = A_j.
+ * KNOWN LIMIT: a frame nobody transmitted finds a live address with probability about (nbits - 5) * fleet / 2^24 per dropped
+ * address/parity packet -- 2.6e-4 for 40 aircraft alive and a long reply, one in six for 25 000 -- so the repair is useless near
+ * the map's capacity.  Nothing guards against it: the setting is for a receiver that hears a modest fleet.
+ * The setting belongs to the context, survives am_reset and am_set_rate, takes effect with the next call and is inert while the
+ * gate is off.  Covered: what the gate covers.  NOT covered: am_spipe_* and the time shards, as for the gate.
+ * AM_EINVAL for max_bits outside 0..1.
+ * Stats: since am_create, of scans the library accepted: packets repaired, packets dropped as ambiguous.  The gate's `dropped`
+ * does not include a repaired packet; `passed` keeps its meaning (kept by step 2 as sliced).  Either pointer may be null. */
+AM_API int    am_set_address_repair(am_ctx *ctx, int max_bits);
+AM_API int    am_get_address_repair(const am_ctx *ctx);
+AM_API int    am_get_address_repair_stats(const am_ctx *ctx, uint64_t *repaired, uint64_t *ambiguous);
 /* ---- batches in flight ---------------------------------------------------------------------------------------
  * Under GNU Radio every block of rx_path runs in its own thread, so the slicer works on burst k while the preamble
  * block scans ahead (thread-per-block scheduler; python/rx_path.py wires five blocks).  The counterpart here: the
@@ -237,6 +267,10 @@ AM_API int am_pipe_get_fix_errors(const am_pipe *pipe);
  * stream: its own empty map).  AM_EINVAL while batches are in flight, and for what am_set_address_gate refuses. */
 AM_API int am_pipe_set_address_gate(am_pipe *pipe, int mode, double ttl_seconds);
 AM_API int am_pipe_get_address_gate(const am_pipe *pipe, int *mode, double *ttl_seconds);
+/* am_set_address_repair for every context behind the handle.  AM_EINVAL while batches are in flight, and for max_bits
+ * outside 0..1. */
+AM_API int am_pipe_set_address_repair(am_pipe *pipe, int max_bits);
+AM_API int am_pipe_get_address_repair(const am_pipe *pipe);
 
 /* ---- ONE continuing stream with several of its chunks in flight ---------------------------------------------------
  * The reference's preamble block is a streaming block: general_work() resumes where the last call stopped (lib/preamble_impl.cc:

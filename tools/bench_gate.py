@@ -12,6 +12,10 @@ Kernel times come from a run of its own under the profiler (tracing slows the ho
 The gate's kernels have names of their own (am_k_gate_teach, am_k_gate_test, am_k_gate_ticket) and the slicing kernel is another
 instantiation (am_k_extract_slice_iq<32, 0, 1>), so the kernel statistics separate them by themselves.
 
+--repair adds a fourth leg "1r": mode 1 with am_set_address_repair(1), interleaved with the others, so that "1r" against "1" is
+what the repair costs on top of the gate (its kernels: am_k_gate_test<1>, am_k_gate_repair, am_k_gate_repair_ticket, and the
+slicing kernel's <.., 2> instantiation); its packets are compared with tests/aprepair_common.py.
+
 Prints one JSON line per capture."""
 import argparse
 import json
@@ -42,6 +46,7 @@ def main(argv=None):
     ap.add_argument("--seconds", type=float, default=1.0, help="signal seconds per step")
     ap.add_argument("--ttl", type=float, default=60.0, help="window in seconds")
     ap.add_argument("--captures", default="stress,low_snr")
+    ap.add_argument("--repair", action="store_true", help="add the leg 1r: mode 1 with am_set_address_repair(1)")
     ap.add_argument("--profile", action="store_true", help="steps only, mode by mode (for a run under rocprofv3)")
     ap.add_argument("--no-definition", action="store_true", help="skip the comparison with the definition on the CPU")
     args = ap.parse_args(argv)
@@ -62,6 +67,10 @@ def main(argv=None):
         for mode in (0, 1, 2):
             ctxs[mode] = _capi.Context(RATE, 7.0, True, device=0, lib=lib)
             ctxs[mode].set_address_gate(mode, args.ttl)
+        if args.repair:
+            ctxs["1r"] = _capi.Context(RATE, 7.0, True, device=0, lib=lib)
+            ctxs["1r"].set_address_gate(1, args.ttl)
+            ctxs["1r"].set_address_repair(1)
         out = {"capture": name, "rate": RATE, "seconds": args.seconds, "bursts_per_second": lam, "snr_db": list(snr),
                "aircraft": naddr, "ttl_seconds": args.ttl, "steps": args.steps, "modes": {}}
         last = {}
@@ -93,6 +102,12 @@ def main(argv=None):
                 "device_ms_per_step_median": float(np.median(d)), "device_ms_per_step_min": float(d.min()),
                 "packets": int(len(last[m])), "taught": st["taught"] // per, "passed": st["passed"] // per,
                 "dropped": st["dropped"] // per, "not_learned": st["not_learned"]}
+            if m == "1r":
+                rs = ctxs[m].address_repair_stats()
+                out["modes"][m].update(repaired=rs["repaired"] // per, ambiguous=rs["ambiguous"] // per)
+        if args.repair:
+            for key in ("ms_per_step_median", "device_ms_per_step_median"):
+                out["modes"]["1r"][key.replace("_median", "") + "_vs_gate"] = out["modes"]["1r"][key] / out["modes"]["1"][key]
         for m in ("1", "2"):
             for key in ("ms_per_step_median", "device_ms_per_step_median"):
                 out["modes"][m][key.replace("_median", "") + "_vs_off"] = out["modes"][m][key] / out["modes"]["0"][key]
@@ -107,6 +122,12 @@ def main(argv=None):
                 k = gc.gate(pk, m, gc.ttl_samples(args.ttl, RATE))
                 out["modes"][str(m)]["equals_definition"] = bool(pk[k].tobytes() == last[m].tobytes())
                 out["modes"][str(m)]["false_ap_packets_kept"] = int((k & isap & ~true).sum())
+            if args.repair:
+                import aprepair_common as ar
+                want, keep, fixed, amb = ar.repair(pk, 1, gc.ttl_samples(args.ttl, RATE))
+                r = want[want["reserved"][:, 1] != 0]
+                out["modes"]["1r"].update(equals_definition=bool(want.tobytes() == last["1r"].tobytes()),
+                                          repaired_not_transmitted=int((~gc.transmitted(r, truth)).sum()))
         for c in ctxs.values():
             c.close()
         del dev

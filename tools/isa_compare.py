@@ -7,7 +7,12 @@ Every kernel whose name contains "slice" is compared as its instruction stream A
 registers, LDS, scratch, kernarg size), comments stripped, basic-block labels renumbered per function and the kernel's own
 mangled name replaced by a placeholder.  A kernel `name<..., 0>` of the second listing is matched with `name<...>` of the
 first: the last template argument, = 0, is the only difference in the name (FIX when the repair was added, GATE when the
-address gate was: `am_k_extract_slice_iq<32, 1, 0>` is matched with `am_k_extract_slice_iq<32, 1>`).  Exit status 1 if any pair differs."""
+address gate was: `am_k_extract_slice_iq<32, 1, 0>` is matched with `am_k_extract_slice_iq<32, 1>`).  Exit status 1 if any pair differs.
+
+    python tools/isa_compare.py --same-names parent.s this.s
+is for a commit that adds a VALUE of an existing template argument instead (GATE = 2 for am_set_address_repair): every kernel
+whose name contains "slice" or "gate" and which the first listing has under the same name is compared with that one; the others
+are listed as new."""
 import re
 import subprocess
 import sys
@@ -41,7 +46,26 @@ def demangle(names):
     return {n: d.split("(")[0].replace("void ", "") for n, d in zip(names, res)}
 
 
+def same_names(a, b):
+    na, nb = demangle([k for k in a]), demangle([k for k in b if "slice" in k or "gate" in k])
+    first = {d: k for k, d in na.items()}
+    worst = 0
+    for k, d in sorted(nb.items(), key=lambda kv: kv[1]):
+        lines, info = b[k]
+        text = "%-36s %5d lines  %s" % (d, len(lines), " ".join("%s=%s" % kv for kv in info.items()))
+        if d in first:
+            same = a[first[d]][0] == lines and a[first[d]][1] == info
+            text += "   == the first listing's: %s" % ("IDENTICAL" if same else "DIFFERENT")
+            worst |= not same
+        else:
+            text += "   new"
+        print(text)
+    sys.exit(int(worst))
+
+
 def main():
+    if sys.argv[1] == "--same-names":
+        same_names(kernels(sys.argv[2]), kernels(sys.argv[3]))
     a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
     na, nb = demangle([k for k in a if "slice" in k]), demangle([k for k in b if "slice" in k])
     first = {d: k for k, d in na.items()}

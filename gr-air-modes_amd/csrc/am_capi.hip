@@ -31,8 +31,10 @@ static inline double am_now_us()
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// a device buffer of T that only grows; cap is in BYTES
+template <class T>
 struct DevBuf {
-    void *p = nullptr;
+    T *p = nullptr;
     size_t cap = 0;
 };
 
@@ -91,8 +93,8 @@ struct TailReq {
     bool copy_tail = false;            // time shards: am_shard_keep_tail's copy goes between the slicing and the ticket
     bool has_entry = false;            // time shards: the start position is composed on the device from `entry`
     am_entry_src entry;
-    const uint32_t *flag_src = nullptr;   // this device word comes to the host with the completion ticket (pin_scalars[4])
-    const uint64_t *word_src = nullptr;   // ... and this 64-bit one (pin_scalars[12..13]: where the scan left the chunk)
+    const uint32_t *flag_src = nullptr;   // this device word comes to the host with the completion ticket (pin_scalars[AM_PW_FLAG])
+    const uint64_t *word_src = nullptr;   // ... and this 64-bit one (pin_scalars[AM_PW_EXIT]: where the scan left the chunk)
     hipEvent_t walk_event = nullptr;      // recorded behind the block walk (am_spipe: what the next chunk's resolve step waits for)
 };
 
@@ -109,7 +111,7 @@ struct am_ctx {
     int spc_hi = 0;               // samples per chip rounded UP: look-ahead sizes (= spc for a multiple of 2 MHz)
     bool frac = false;            // the rate is not a multiple of 2 MHz: rate-generic kernels, geometry from `geom`
     am_geom geom;                 // the preamble block's geometry in the reference's float arithmetic
-    DevBuf chip_idx;              // [240] int: sample offset of soft chip j, int(j * samples per chip)
+    DevBuf<int> chip_idx;         // [240]: sample offset of soft chip j, int(j * samples per chip)
     float thr_db = 0.0f;
     float thr_lin = 0.0f;
     int use_pmf = 0;
@@ -118,16 +120,18 @@ struct am_ctx {
     int gate_mode = 0;            // 0: off; 1: address/parity replies need a taught address; 2: and reserved formats are dropped
     double gate_ttl_s = 60.0;     // how long a taught address lives, seconds
     uint64_t gate_ttl = 1;        // ... in item counts: max(1, (uint64)(gate_ttl_s * rate)), formed when a scan is launched
-    DevBuf gate_rec, gate_scratch, gate_map, gate_multi;   // records of the scan, the call's table, the context's map, K streams' limits
+    DevBuf<am_gate_rec> gate_rec;                          // records of the scan
+    DevBuf<unsigned long long> gate_scratch, gate_map;     // the call's table, the context's map
+    DevBuf<unsigned long long> gate_multi;                 // K streams' offsets, then their emit limits (signed)
     uint64_t *pin_gate_multi = nullptr;   // pinned staging copy of gate_multi
-    const void *gate_rec_told = nullptr;  // the record array whose address scalars[AM_GATE_REC_WORD] holds
+    const void *gate_rec_told = nullptr;  // the record array whose address scalars[AM_SW_GATE_REC] holds
     bool gate_dirty = false;      // the map has been taught since it was last emptied
-    bool gate_live = false;       // the scan in flight / last collected ran with the gate: pin_scalars[9..11] are its counters
+    bool gate_live = false;       // the scan in flight / last collected ran with the gate: pin_scalars[AM_PW_GATE_*] are its counters
     am_gate_args ga = {};         // ... and its arguments (am_k_gate_commit gets them again, with the count the host accepted)
     uint64_t gate_stat[3] = {0, 0, 0};   // taught, passed, dropped since am_create (accepted scans only)
     // am_set_address_repair: one wrong bit of an address/parity reply the gate fails, found among the addresses alive
     int gate_repair = 0;          // 0: off; 1: on (inert while gate_mode is 0)
-    DevBuf gate_list;             // counters and the hit indices of the failed address/parity records (am_gate_args.rl)
+    DevBuf<uint32_t> gate_list;   // counters and the hit indices of the failed address/parity records (am_gate_args.rl)
     uint64_t repair_stat[2] = {0, 0};    // repaired, ambiguous since am_create (accepted scans only)
     int tile = 0;
     // Speculative launches: the candidate count of a scan is only known on the device when its kernels
@@ -167,17 +171,21 @@ struct am_ctx {
     bool poison = false;          // (test builds: AIRMODES_POISON=1) NaN-fill the sparse bb / reference-level arrays before every scan
     bool fused_refine = true;        // 64 Msps (round 6): list + rows + refinement in one launch, the rows in LDS (am_k_refine_seg); test builds:
                                      // AIRMODES_FUSED_REFINE=0 keeps am_k_gather_wg<1> + am_k_refine_late with a maximum per row
-    DevBuf bbmax;
+    DevBuf<float> bbmax;
     bool allow_stream = true;        // (test builds: AIRMODES_FE=2) keeps the tile kernel (am_k_fe2, dense bb) where the streaming one would run
     // the scan whose records are resident: assigned whole when a scan starts (new_scan), read by its tail -- in the same call, or
     // in a later one (am_shard_scan then am_shard_resolve*, am_submit_iq then am_collect)
     Scan scan;
+    // ... as the launchers take them: the buffers, and the scan's count (or, while a refinement is being launched, the count it is
+    // launched for)
+    am_records records(uint32_t M, const uint32_t *Mp) const { return {pos.p, e.p, tgt.p, inavg.p, valid.p, jump.p, M, Mp}; }
+    am_records records() const { return records(scan.M, scan.Mp); }
     char err[256] = "";
 
     // "rx_time" stream tags still able to stamp a future preamble, ascending offsets (am_set_rx_time);
     // tt_dev mirrors them on the device for the extraction kernel
     std::vector<am_time_tag> tt;
-    DevBuf tt_dev;
+    DevBuf<am_time_tag> tt_dev;
     am_time_tag *pin_tt = nullptr;   // pinned staging copy of the K streams' tags (multi_begin)
 
     // stream state (absolute sample indices)
@@ -188,26 +196,33 @@ struct am_ctx {
     // the block-level preamble as a STREAM (am_preamble_stream): items so far, first undecided position, where the greedy scan
     // resumes, and the tail of both inputs that the next call's decisions still read
     uint64_t pb_total = 0, pb_next = 0, pb_cur = 0, pb_carry_abs0 = 0, pb_carry_n = 0;
-    DevBuf pb_bb, pb_avg;
+    DevBuf<float> pb_bb, pb_avg;
     uint64_t total_in = 0;    // samples received so far
     uint64_t next_pos = 0;    // first position whose preamble test is still undecided
     uint64_t chain_cur = 0;   // position at which the greedy scan resumes
     uint64_t carry_abs0 = 0;
     uint64_t carry_n = 0;
-    DevBuf carry, carry2;
+    DevBuf<float> carry, carry2;
 
     // work buffers (grow only)
-    DevBuf raw_in;                // raw bytes of a host chunk in a native sample format (am_process_samples, am_unpack)
-    DevBuf src, bb, avg, cand_seg, inavg, blk_cnt, blk_off, pos, e, tgt, valid,
-        jump, emit_idx, dcount, off_local, blk_tot2, blk_base2, energy, bits, seg_base,
-        cblk_cnt, cblk_off, scalars, bursts, tags, packets, crc_pow, recs, cscratch, dc_m1, dc_y, wgmax;
+    DevBuf<unsigned char> raw_in; // raw bytes of a host chunk in a native sample format (am_process_samples, am_unpack)
+    DevBuf<float> src, bb, avg, inavg, bursts, dc_m1, dc_y, wgmax;
+    DevBuf<uint32_t> cand_seg, blk_cnt, blk_off, pos, e, tgt, jump, dcount, off_local, blk_tot2, blk_base2, bits, seg_base, cblk_cnt,
+        cblk_off, crc_pow;
+    DevBuf<uint8_t> valid;
+    DevBuf<uint4> emit_idx;       // one record per hit (am_emit_args)
+    DevBuf<double> energy;
+    DevBuf<uint32_t> scalars;     // the device scalar block (am_scalar_word)
+    DevBuf<uint32_t> cscratch;    // the chain's tables (am_chain_scratch_bytes); the kernels keep 16-bit head links in part of it
+    DevBuf<am_tag> tags;
+    DevBuf<am_packet> packets;
     int fe_wgs_per_cu = 0;                // persistent front-end workgroups per CU (0: as many as fit; am_pipe: one fewer)
-    DevBuf lb_dc, lb_mark;      // slots of the chained scans (am_chain_prefix): zero at allocation, tagged with lb_epoch
-    DevBuf lb_entry;            // ... and of the block entries the walker of am_k_cblk_visit hands its markers ({epoch, entry} per block)
+    DevBuf<unsigned long long> lb_dc, lb_mark;      // slots of the chained scans (am_chain_prefix): zero at allocation, tagged with lb_epoch
+    DevBuf<unsigned long long> lb_entry;            // ... and of the block entries the walker of am_k_cblk_visit hands its markers ({epoch, entry} per block)
     int walk_mode = AM_WALK_AUTO;   // test builds: AIRMODES_WALK forces the one- or the two-launch form of the chain visit
-    bool walk_clear = false;        // chain_prepare has cleared scalars[0 .. 1] and no visit has raised them since (the one-launch form needs it)
+    bool walk_clear = false;        // chain_prepare has cleared scalars[AM_SW_RESUME], [AM_SW_HIT] and no visit has raised them since (the one-launch form needs it)
     uint32_t lb_epoch = 0;
-    uint32_t tk_base[2] = {0, 0};     // value of the ticket counters scalars[10], [11] when the next launch on them starts (am_chain_place)
+    uint32_t tk_base[2] = {0, 0};     // value of the ticket counters scalars[AM_SW_TICKET_SCAN], [AM_SW_TICKET_MARK] when the next launch on them starts (am_chain_place)
 
     // results of the last scan
     std::vector<am_packet> h_packets;   // am_slicer_work: every sliced burst, reserved[0] = accepted
@@ -225,7 +240,7 @@ struct am_ctx {
     void *keep_dst = nullptr;           // am_shard_keep_tail: copied between a resolve step's slicing and its completion
     const void *keep_src = nullptr;
     uint64_t keep_bytes = 0;
-    DevBuf shard_exit;                  // device word: where the scan left this context's chunk in the last resolved step (0: none)
+    DevBuf<uint64_t> shard_exit;        // device word: where the scan left this context's chunk in the last resolved step (0: none)
 
     // pinned host memory the tail kernels write into directly
     am_packet *pin_packets = nullptr;
@@ -259,15 +274,18 @@ int fail(am_ctx *c, int code, const char *what, hipError_t rc = hipSuccess)
         if (rc__ != hipSuccess) return fail((c), AM_EHIP, #call, rc__);      \
     } while (0)
 
-int ensure(am_ctx *c, DevBuf &b, size_t bytes)
+template <class T>
+int ensure(am_ctx *c, DevBuf<T> &b, size_t bytes)
 {
     if (bytes <= b.cap && b.p) return AM_OK;
     if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
     // grow with headroom (hipFree / hipMalloc synchronise the whole device): half as much again for the
     // per-candidate arrays, whose size follows the traffic; an eighth for the big sample arrays
     size_t want = bytes + (bytes < ((size_t)64 << 20) ? bytes / 2 + ((size_t)256 << 10) : bytes / 8);
-    hipError_t rc = hipMalloc(&b.p, want);
-    if (rc != hipSuccess) { b.p = nullptr; return fail(c, AM_ENOMEM, "hipMalloc", rc); }
+    void *mem = nullptr;
+    hipError_t rc = hipMalloc(&mem, want);
+    if (rc != hipSuccess) return fail(c, AM_ENOMEM, "hipMalloc", rc);
+    b.p = static_cast<T *>(mem);
     b.cap = want;
     return AM_OK;
 }
@@ -279,7 +297,7 @@ int ensure(am_ctx *c, DevBuf &b, size_t bytes)
     } while (0)
 
 // slots of a chained scan for n workgroups: zeroed when (re)allocated (epoch 0 is never used)
-int ensure_slots(am_ctx *c, DevBuf &b, size_t n)
+int ensure_slots(am_ctx *c, DevBuf<unsigned long long> &b, size_t n)
 {
     const size_t bytes = (n + 8) * sizeof(unsigned long long);
     if (bytes <= b.cap && b.p) return AM_OK;
@@ -295,21 +313,20 @@ int ensure_slots(am_ctx *c, DevBuf &b, size_t n)
 uint32_t next_epoch(am_ctx *c)
 {
     if (++c->lb_epoch == 0) {
-        for (DevBuf *b : {&c->lb_dc, &c->lb_mark, &c->lb_entry})
+        for (DevBuf<unsigned long long> *b : {&c->lb_dc, &c->lb_mark, &c->lb_entry})
             if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap, c->stream);
         c->lb_epoch = 1;
     }
     return c->lb_epoch;
 }
 
-// the small device-side scalar block of a context: [0] resume position, [1] hit flag, [4..5] time-shard entry / overflow flag,
-// zero when it is allocated
+// the small device-side scalar block of a context (its words: am_scalar_word, am_internal.h), zero when it is allocated
 int ensure_scalars(am_ctx *c)
 {
     if (c->scalars.p) return AM_OK;
-    int rc = ensure(c, c->scalars, 16 * sizeof(uint32_t));
+    int rc = ensure(c, c->scalars, AM_SW_WORDS * sizeof(uint32_t));
     if (rc != AM_OK) return rc;
-    if (hipMemsetAsync(c->scalars.p, 0, 16 * sizeof(uint32_t), c->stream) != hipSuccess) return fail(c, AM_EHIP, "hipMemsetAsync");
+    if (hipMemsetAsync(c->scalars.p, 0, AM_SW_WORDS * sizeof(uint32_t), c->stream) != hipSuccess) return fail(c, AM_EHIP, "hipMemsetAsync");
     return AM_OK;
 }
 
@@ -323,22 +340,24 @@ int ensure_shard_exit(am_ctx *c)
     return AM_OK;
 }
 
-// the pinned scalar block the tail kernels write into: [0..2] results of the slice launch, [3..4] time shards, [5] chained-scan
-// error, [8] completion ticket, [9..11] address gate, [12..13] a time chunk's exit word, [14..15] the gate's repair
+// the pinned scalar block the tail kernels write into (its words: am_pinned_word, am_internal.h)
 int ensure_pin_scalars(am_ctx *c)
 {
     if (c->pin_scalars) return AM_OK;
-    HIPCHK(c, hipHostMalloc((void **)&c->pin_scalars, 16 * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
-    memset(c->pin_scalars, 0, 16 * sizeof(uint32_t));
+    HIPCHK(c, hipHostMalloc((void **)&c->pin_scalars, AM_PW_WORDS * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
+    memset(c->pin_scalars, 0, AM_PW_WORDS * sizeof(uint32_t));
     return AM_OK;
 }
 
-void release(DevBuf &b)
+template <class T>
+void release(DevBuf<T> &b)
 {
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
     b.cap = 0;
 }
+template <class... T>
+void release_all(DevBuf<T> &...b) { (release(b), ...); }
 
 // x^i mod G(x), G = 0x1FFF409: the syndrome of a frame is the XOR of these over its set bits
 void crc_powers(uint32_t *t, int n)
@@ -415,7 +434,7 @@ void reset_stream(am_ctx *c)
     c->shard_ready = false;
     c->tt.clear();            // item offsets restart with the stream
     if (c->gate_dirty) {      // ... and so does what the address gate has learned (the counters in front of the map stay)
-        (void)hipMemsetAsync((unsigned long long *)c->gate_map.p + 4, 0, (size_t)2 * AM_GATE_MAP_SLOTS * sizeof(unsigned long long), c->stream);
+        (void)hipMemsetAsync(c->gate_map.p + 4, 0, (size_t)2 * AM_GATE_MAP_SLOTS * sizeof(unsigned long long), c->stream);
         (void)hipMemsetAsync(c->gate_map.p, 0, sizeof(unsigned long long), c->stream);      // slots taken
         c->gate_dirty = false;
     }
@@ -431,7 +450,7 @@ inline uint64_t zero_pad(int spc_hi) { return (uint64_t)260 * (uint64_t)spc_hi +
 // the thread blocks in the runtime.
 hipError_t wait_for_ticket(am_ctx *c, uint32_t seq)
 {
-    volatile uint32_t *word = c->pin_scalars + 8;
+    volatile uint32_t *word = c->pin_scalars + AM_PW_TICKET;
     const double t0 = am_now_us();
     unsigned spins = 0;
     while (*word != seq) {
@@ -477,8 +496,8 @@ int apply_dcblock(am_ctx *c, const float **src, uint64_t *src_abs0, uint64_t src
     ENSURE(c, c->dc_y, yn * 2 * sizeof(float));
     ENSURE(c, c->dc_m1, (yn + H / 2 + 1) * 2 * sizeof(float));
     HIPCHK(c, am_launch_dcblock(*src, (long long)*src_abs0, (long long)src_abs1, (long long)need0, (long long)yn,
-                                c->spc, (float *)c->dc_m1.p, (float *)c->dc_y.p, c->stream));
-    *src = (const float *)c->dc_y.p;
+                                c->spc, c->dc_m1.p, c->dc_y.p, c->stream));
+    *src = c->dc_y.p;
     *src_abs0 = need0;
     return AM_OK;
 }
@@ -532,18 +551,18 @@ int run_refine(am_ctx *c, Scan &sc, uint32_t spec_cap = 0)
     if (nseg == 0) return AM_OK;
     if (int rcs = ensure_scalars(c); rcs != AM_OK) return rcs;
     const bool spec = spec_cap && kind != REFINE_GENERIC;
-    const uint32_t *count_ptr = (const uint32_t *)c->blk_off.p + nseg;       // device-side total
+    const uint32_t *count_ptr = c->blk_off.p + nseg;       // device-side total
     if (reads_bitmap(kind)) {
         // streaming front end: the flat list is laid out from the per-workgroup counts by the gather kernel itself, which also
         // leaves the total (blk_off[0]); only a scan that must know its count up front adds the counts first
-        count_ptr = (const uint32_t *)c->blk_off.p;
+        count_ptr = c->blk_off.p;
         if (!spec) {
             ENSURE(c, c->seg_base, ((size_t)fe.nwg + 2) * sizeof(uint32_t));
-            HIPCHK(c, am_launch_scan_u32((uint32_t *)c->blk_cnt.p, (uint32_t *)c->seg_base.p, fe.nwg, c->stream));
-            count_ptr = (const uint32_t *)c->seg_base.p + fe.nwg;
+            HIPCHK(c, am_launch_scan_u32(c->blk_cnt.p, c->seg_base.p, fe.nwg, c->stream));
+            count_ptr = c->seg_base.p + fe.nwg;
         }
     } else
-        HIPCHK(c, am_launch_scan_u32((uint32_t *)c->blk_cnt.p, (uint32_t *)c->blk_off.p, nseg, c->stream));
+        HIPCHK(c, am_launch_scan_u32(c->blk_cnt.p, c->blk_off.p, nseg, c->stream));
     uint32_t M = 0;
     const uint32_t *Mp = nullptr;
     if (spec) {
@@ -560,6 +579,7 @@ int run_refine(am_ctx *c, Scan &sc, uint32_t spec_cap = 0)
         ENSURE(c, c->inavg, ((size_t)M + 1) * sizeof(float));
         ENSURE(c, c->valid, (size_t)M + 1);
         if (kind != REFINE_GENERIC) ENSURE(c, c->jump, ((size_t)M + 1) * sizeof(uint32_t));   // (they write the chain's successors)
+        const am_refine_in in = {bb, avg, c->thr_lin, end_j};
         switch (kind) {
         case REFINE_SEG:
             // 64 Msps: flat positions, bb rows (in LDS), late-peak decisions, quiet zones, records and the chain's successors in ONE
@@ -567,21 +587,16 @@ int run_refine(am_ctx *c, Scan &sc, uint32_t spec_cap = 0)
 #if defined(AM_TEST_KNOBS)
             if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: am_k_refine_seg, %u segments of %u words, capacity %u\n", fe.nwg, fe.words_per_wg(), M);
 #endif
-            HIPCHK(c, am_launch_refine_seg((uint32_t *)c->bits.p, (uint32_t *)c->blk_cnt.p, (const float *)c->wgmax.p, fe, M, sc.rows, avg,
-                                           c->thr_lin, end_j, (uint32_t *)c->pos.p, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p,
-                                           (float *)c->inavg.p, (uint8_t *)c->valid.p, (uint32_t *)c->jump.p, (uint32_t *)c->blk_off.p,
-                                           c->stream));
+            HIPCHK(c, am_launch_refine_seg({c->bits.p, c->blk_cnt.p, c->wgmax.p}, fe, sc.rows, in, c->records(M, Mp), c->blk_off.p, c->stream));
             break;
         case REFINE_LATE:
         case REFINE_LATE_ROWS:
             // streaming front end: candidates arrive as a bitmap; flat positions, then late-peak decisions, quiet zones,
             // records and the chain's successors in one launch (am_k_refine_late)
-            HIPCHK(c, am_launch_gather_wg((uint32_t *)c->bits.p, (uint32_t *)c->blk_cnt.p, fe, M, (uint32_t *)c->pos.p,
-                                          (uint32_t *)c->blk_off.p, c->stream, kind == REFINE_LATE_ROWS ? &sc.rows : nullptr));
-            HIPCHK(c, am_launch_refine_late(bb, avg, (uint32_t *)c->pos.p, M, c->spc, c->thr_lin, end_j, (uint32_t *)c->e.p,
-                                            (uint32_t *)c->tgt.p, (float *)c->inavg.p, (uint8_t *)c->valid.p,
-                                            (uint32_t *)c->jump.p, c->stream, Mp, (const float *)c->wgmax.p, fe,
-                                            kind == REFINE_LATE_ROWS ? sc.rows.bb_max : nullptr));
+            HIPCHK(c, am_launch_gather_wg(c->bits.p, c->blk_cnt.p, fe, M, c->pos.p,
+                                          c->blk_off.p, c->stream, kind == REFINE_LATE_ROWS ? &sc.rows : nullptr));
+            HIPCHK(c, am_launch_refine_late(in, c->spc, c->records(M, Mp), c->wgmax.p, fe, kind == REFINE_LATE_ROWS ? sc.rows.bb_max : nullptr,
+                                            c->stream));
             break;
         case REFINE_SPLIT: {
 #if AM_WITH_TILE_KERNEL
@@ -593,30 +608,21 @@ int run_refine(am_ctx *c, Scan &sc, uint32_t spec_cap = 0)
             ENSURE(c, c->blk_tot2, ((size_t)nb + 1) * sizeof(uint32_t));
             ENSURE(c, c->blk_base2, ((size_t)nb + 2) * sizeof(uint32_t));
             ENSURE(c, c->energy, (size_t)(ebound + 2) * sizeof(double));
-            HIPCHK(c, am_launch_gather_pos((uint32_t *)c->cand_seg.p, seg_stride, (uint32_t *)c->blk_off.p, nseg, M,
-                                           c->spc, (uint32_t *)c->pos.p, (uint32_t *)c->dcount.p, c->stream, Mp));
+            HIPCHK(c, am_launch_gather_pos(c->cand_seg.p, seg_stride, c->blk_off.p, nseg, M, c->spc, c->pos.p, c->dcount.p, c->stream, Mp));
             // compact index of each candidate's first energy: one chained scan of the counts (global offsets)
             if (int rc = ensure_slots(c, c->lb_dc, nb); rc != AM_OK) return rc;
-            HIPCHK(c, am_launch_exscan_chain((uint32_t *)c->dcount.p, (uint32_t *)c->off_local.p, M,
-                                             (unsigned long long *)c->lb_dc.p, next_epoch(c), (uint32_t *)c->blk_base2.p + nb,
-                                             (uint32_t *)c->scalars.p + 9, (uint32_t *)c->scalars.p + 10, &c->tk_base[0],
+            HIPCHK(c, am_launch_exscan_chain(c->dcount.p, c->off_local.p, M, c->lb_dc.p, next_epoch(c), c->blk_base2.p + nb,
+                                             c->scalars.p + AM_SW_CHAIN_ERR, c->scalars.p + AM_SW_TICKET_SCAN, &c->tk_base[0],
                                              c->stream, Mp));
-            HIPCHK(c, am_launch_energy(bb, (uint32_t *)c->pos.p, (uint32_t *)c->dcount.p, (uint32_t *)c->off_local.p,
-                                       nullptr, M, c->spc, (double *)c->energy.p, c->stream, Mp));
-            HIPCHK(c, am_launch_cand(bb, avg, (uint32_t *)c->pos.p, (uint32_t *)c->dcount.p,
-                                     (uint32_t *)c->off_local.p, nullptr, (double *)c->energy.p, M,
-                                     c->spc, c->thr_lin, end_j, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p,
-                                     (float *)c->inavg.p, (uint8_t *)c->valid.p, (uint32_t *)c->jump.p, c->stream, Mp));
+            HIPCHK(c, am_launch_energy(bb, c->pos.p, c->dcount.p, c->off_local.p, nullptr, M, c->spc, c->energy.p, c->stream, Mp));
+            HIPCHK(c, am_launch_cand(in, c->dcount.p, c->off_local.p, nullptr, c->energy.p, c->spc, c->records(M, Mp), c->stream));
             break;
 #else
             return fail(c, AM_EINVAL, "internal: no kernel for this refinement");
 #endif
         }
         case REFINE_GENERIC:
-            HIPCHK(c, am_launch_refine(bb, avg, c->geom, c->thr_lin, (uint32_t *)c->cand_seg.p, seg_stride,
-                                       (uint32_t *)c->blk_off.p, nseg, M, (uint32_t *)c->pos.p,
-                                       (uint32_t *)c->e.p, (uint32_t *)c->tgt.p, (float *)c->inavg.p,
-                                       (uint8_t *)c->valid.p, c->stream));
+            HIPCHK(c, am_launch_refine(in, c->geom, c->cand_seg.p, seg_stride, c->blk_off.p, nseg, c->records(M, nullptr), c->stream));
             break;
         }
         sc.jump_ready = kind != REFINE_GENERIC;
@@ -644,8 +650,7 @@ int run_candidates(am_ctx *c, const float *bb, const float *avg, uint32_t j0, ui
     ENSURE(c, c->cand_seg, (size_t)nblk * AM_DET_PER_BLOCK * sizeof(uint32_t));
     ENSURE(c, c->blk_cnt, (size_t)nblk * sizeof(uint32_t));
     ENSURE(c, c->blk_off, ((size_t)nblk + 1) * sizeof(uint32_t));
-    HIPCHK(c, am_launch_detect(bb, avg, j0, j1, c->geom, c->thr_lin, (uint32_t *)c->cand_seg.p,
-                               (uint32_t *)c->blk_cnt.p, nblk, c->stream));
+    HIPCHK(c, am_launch_detect(bb, avg, j0, j1, c->geom, c->thr_lin, c->cand_seg.p, c->blk_cnt.p, nblk, c->stream));
     sc.ref = {bb, avg, nblk, AM_DET_PER_BLOCK, REFINE_GENERIC};
     return run_refine(c, sc);
 }
@@ -692,17 +697,17 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
         if (kind == REFINE_LATE_ROWS) {
             // one float per array chip: the largest bb of every row formed (am_k_refine_late: whole chips of a quiet zone)
             ENSURE(c, c->bbmax, ((size_t)(out_n / 32) + 64) * sizeof(float));
-            sc.rows.bb_max = (float *)c->bbmax.p;
+            sc.rows.bb_max = c->bbmax.p;
             if (c->poison) HIPCHK(c, hipMemsetAsync(c->bbmax.p, 0xFF, ((size_t)(out_n / 32) + 64) * sizeof(float), c->stream));
         }
         const am_fe_stream_req r = {src, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0, (long long)out_n,
-                                    rows_from_iq(kind) ? nullptr : bb, (float *)c->avg.p, j0, j1, c->use_pmf, c->s1, c->sL, c->thr_lin,
-                                    (uint32_t *)c->bits.p, (uint32_t *)c->blk_cnt.p, (float *)c->wgmax.p};
+                                    rows_from_iq(kind) ? nullptr : bb, c->avg.p, j0, j1, c->use_pmf, c->s1, c->sL, c->thr_lin,
+                                    c->bits.p, c->blk_cnt.p, c->wgmax.p};
         HIPCHK(c, am_launch_fe4(c->spc, r, &sc.fe, c->stream, c->fe_wgs_per_cu, kind == REFINE_SEG));
         HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
         c->dom_timed = true;
         sc.sparse = true;
-        sc.ref = {bb, (const float *)c->avg.p, sc.fe.nwg, 0, kind, end_j};
+        sc.ref = {bb, c->avg.p, sc.fe.nwg, 0, kind, end_j};
         return run_refine(c, sc, may_speculate ? spec_capacity(c, j1 - j0) : 0u);
     }
 #if AM_WITH_TILE_KERNEL
@@ -718,11 +723,11 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
     float *avg_sparse = nullptr;
     if (!avg) {
         ENSURE(c, c->avg, (out_n + zero_pad(c->spc_hi)) * sizeof(float));
-        avg_sparse = (float *)c->avg.p;
+        avg_sparse = c->avg.p;
     }
     HIPCHK(c, am_launch_fe2(c->spc, src, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0,
-                            (long long)out_n, bb, avg, j0, j1, c->use_pmf, c->s1, c->sL, c->thr_lin, (uint32_t *)c->cand_seg.p,
-                            avg_sparse, (uint32_t *)c->blk_cnt.p, &nt, &tl, c->stream));
+                            (long long)out_n, bb, avg, j0, j1, c->use_pmf, c->s1, c->sL, c->thr_lin, c->cand_seg.p,
+                            avg_sparse, c->blk_cnt.p, &nt, &tl, c->stream));
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     c->dom_timed = true;
     sc.ref = {bb, avg_sparse ? avg_sparse : avg, nt, tl, REFINE_SPLIT, end_j};
@@ -744,7 +749,7 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
     ENSURE(c, c->gate_rec, (size_t)(n_max ? n_max : 1) * sizeof(am_gate_rec));
     if (c->gate_rec_told != c->gate_rec.p) {
         const unsigned long long addr = (unsigned long long)(uintptr_t)c->gate_rec.p;
-        HIPCHK(c, hipMemcpyAsync((uint32_t *)c->scalars.p + AM_GATE_REC_WORD, &addr, sizeof(addr), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->scalars.p + AM_SW_GATE_REC, &addr, sizeof(addr), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));          // (addr is a local; only when the array was (re)allocated)
         c->gate_rec_told = c->gate_rec.p;
     }
@@ -757,7 +762,7 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
         HIPCHK(c, hipMemsetAsync(c->gate_map.p, 0, bytes, c->stream));
     }
     am_gate_scratch_layout(a, c->gate_scratch.p, slots);
-    a.rec = (const am_gate_rec *)c->gate_rec.p;
+    a.rec = c->gate_rec.p;
     a.n_ptr = n_ptr;
     a.n = n_max;
     a.hist0 = (unsigned long long)c->geom.hist0;
@@ -765,7 +770,7 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
     if (c->gate_ttl < 1) c->gate_ttl = 1;
     a.ttl = c->gate_ttl;
     a.mode = c->gate_mode;
-    a.t_hdr = (unsigned long long *)c->gate_map.p;
+    a.t_hdr = c->gate_map.p;
     a.t_key = a.t_hdr + 4;
     a.t_last = a.t_key + AM_GATE_MAP_SLOTS;
     a.t_mask = AM_GATE_MAP_SLOTS - 1u;
@@ -773,8 +778,8 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
     a.packets = packets;
     if (c->gate_repair) {
         ENSURE(c, c->gate_list, ((size_t)AM_GATE_RL_HDR + (n_max ? n_max : 1)) * sizeof(uint32_t));
-        a.rl = (uint32_t *)c->gate_list.p;
-        a.crc_pow = (const uint32_t *)c->crc_pow.p;
+        a.rl = c->gate_list.p;
+        a.crc_pow = c->crc_pow.p;
     }
     const size_t K = c->multi_off.size();
     if (K) {
@@ -789,11 +794,14 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
         }
         HIPCHK(c, hipMemcpyAsync(c->gate_multi.p, c->pin_gate_multi, 2 * K * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
         a.K = (uint32_t)K;
-        a.moff = (const unsigned long long *)c->gate_multi.p;
-        a.mem = (const long long *)c->gate_multi.p + K;
+        a.moff = c->gate_multi.p;
+        a.mem = reinterpret_cast<const long long *>(c->gate_multi.p + K);     // (the second half is read signed: -1 = no position may emit)
     }
     return AM_OK;
 }
+
+// Which GATE instantiation the slicing launch of a gated scan runs (gate_prepare has run: c->ga.rl says whether the repair is on)
+int slice_gate(const am_ctx *c, bool gate) { return gate ? (c->ga.rl ? 2 : 1) : 0; }
 
 // The host has accepted the scan whose records are resident and the stream goes on: its first n records' teaches enter the map.
 int gate_commit(am_ctx *c, uint32_t n)
@@ -812,15 +820,12 @@ int gate_commit(am_ctx *c, uint32_t n)
 int chain_prepare(am_ctx *c, bool want_last)
 {
     const uint32_t M = c->scan.M;
-    const uint32_t *Mp = c->scan.Mp;
     if (M == 0) return AM_OK;
     const size_t stride = (size_t)M + 1;
     ENSURE(c, c->jump, stride * sizeof(uint32_t));
     if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
     ENSURE(c, c->cscratch, am_chain_scratch_bytes(M));
-    HIPCHK(c, am_launch_chain_prepare((uint32_t *)c->pos.p, (uint32_t *)c->tgt.p, M, (uint32_t *)c->jump.p,
-                                      (uint32_t *)c->cscratch.p, want_last ? 1 : 0, c->stream, Mp, c->scan.jump_ready ? 1 : 0,
-                                      (uint32_t *)c->scalars.p));
+    HIPCHK(c, am_launch_chain_prepare(c->records(), c->cscratch.p, want_last ? 1 : 0, c->scan.jump_ready ? 1 : 0, c->scalars.p, c->stream));
     c->walk_clear = true;
     return AM_OK;
 }
@@ -829,25 +834,27 @@ int chain_prepare(am_ctx *c, bool want_last)
 int chain_collect(am_ctx *c, const TailReq &req, uint32_t n_max, uint32_t *final_cur)
 {
     c->tail_synced = true;
-    if (c->pin_scalars[5]) {
+    if (c->pin_scalars[AM_PW_CHAIN_ERR]) {
         // a chained scan gave up waiting for a workgroup that never published (am_chain_prefix): nothing of this step is valid
-        (void)hipMemsetAsync((uint32_t *)c->scalars.p + 9, 0, sizeof(uint32_t), c->stream);
+        (void)hipMemsetAsync(c->scalars.p + AM_SW_CHAIN_ERR, 0, sizeof(uint32_t), c->stream);
         return fail(c, AM_EHIP, "a chained scan on the device timed out (a workgroup never published its count)");
     }
     if (c->scan.Mp) {
         // launched for a capacity: now the real candidate count is known
-        c->last_M = c->pin_scalars[2];
-        if (c->pin_scalars[2] > c->scan.M) return AM_RETRY_EXACT;    // capacity too small: results are incomplete
+        c->last_M = c->pin_scalars[AM_PW_CANDIDATES];
+        if (c->pin_scalars[AM_PW_CANDIDATES] > c->scan.M) return AM_RETRY_EXACT;    // capacity too small: results are incomplete
     }
-    const uint32_t n_emit = c->pin_scalars[0];
-    *final_cur = c->pin_scalars[1];
+    const uint32_t n_emit = c->pin_scalars[AM_PW_HITS];
+    *final_cur = c->pin_scalars[AM_PW_RESUME];
     if (n_emit > n_max) return fail(c, AM_EHIP, "internal: more hits than the spacing bound allows");
     c->n_hits = n_emit;
     if (c->gate_live)                                        // (an accepted scan: a repeated one returned above)
     {
-        for (int k = 0; k < 3; k++) c->gate_stat[k] += c->pin_scalars[9 + k];
-        if (c->ga.rl)
-            for (int k = 0; k < 2; k++) c->repair_stat[k] += c->pin_scalars[14 + k];
+        for (int k = 0; k < 3; k++) c->gate_stat[k] += c->pin_scalars[AM_PW_GATE_TAUGHT + k];     // (taught, passed, dropped: consecutive)
+        if (c->ga.rl) {
+            c->repair_stat[0] += c->pin_scalars[AM_PW_REPAIRED];
+            c->repair_stat[1] += c->pin_scalars[AM_PW_AMBIGUOUS];
+        }
     }
     if (!req.keep_bursts) {
         const double TC = am_now_us();
@@ -897,7 +904,7 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
     // everything downstream is launched for that bound and reads the real count on the device.
     // Packets and tags land directly in pinned host memory: one synchronisation for the whole tail.
     const uint32_t n_max = req.max_hits < M ? req.max_hits : M;
-    uint32_t *n_ptr = (uint32_t *)c->cblk_off.p + nb;
+    uint32_t *n_ptr = c->cblk_off.p + nb;
     ENSURE(c, c->emit_idx, (size_t)n_max * sizeof(uint4));     // one record per hit: {candidate, position, refined position, reference level}
     if (int rc = ensure_slots(c, c->lb_mark, nb); rc != AM_OK) return rc;
     // which candidates the scan visits, which of them are hits, and their ordered list -- one launch with the walk for a plain
@@ -910,13 +917,14 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
         if (int rc = ensure_slots(c, c->lb_entry, nb); rc != AM_OK) return rc;
     c->walk_clear = false;
     int fused = 0;
-    HIPCHK(c, am_launch_chain_visit((uint32_t *)c->pos.p, (uint32_t *)c->jump.p, M, cur0, (uint32_t *)c->cscratch.p,
-                                    (uint8_t *)c->valid.p, (uint32_t *)c->e.p, (uint32_t *)c->tgt.p, emit_max, req.own_lo,
-                                    req.own_hi, (uint4 *)c->emit_idx.p, n_ptr, (unsigned long long *)c->lb_mark.p,
-                                    next_epoch(c), (uint32_t *)c->scalars.p + 11, &c->tk_base[1],
-                                    (uint32_t *)c->scalars.p, emit_max == 0xFFFFFFFFu ? 1 : 0, c->stream, Mp,
-                                    req.has_entry ? &req.entry : nullptr, (const float *)c->inavg.p, req.walk_event,
-                                    may_fuse ? (unsigned long long *)c->lb_entry.p : nullptr, c->walk_mode, &fused));
+    const am_records recs = c->records();
+    am_emit_args ea;                                         // (the record pointers and ticket_base: the launcher's)
+    ea.emit_max = emit_max; ea.own_lo = req.own_lo; ea.own_hi = req.own_hi; ea.emit_idx = c->emit_idx.p; ea.n_out = n_ptr;
+    ea.slots = c->lb_mark.p; ea.epoch = next_epoch(c); ea.ticket = c->scalars.p + AM_SW_TICKET_MARK; ea.scalars = c->scalars.p;
+    ea.want_resume = emit_max == 0xFFFFFFFFu ? 1 : 0;
+    const am_walk_req walk = {cur0, c->cscratch.p, req.has_entry ? &req.entry : nullptr, req.walk_event,
+                              may_fuse ? c->lb_entry.p : nullptr, c->walk_mode};
+    HIPCHK(c, am_launch_chain_visit(recs, ea, walk, &c->tk_base[1], &fused, c->stream));
 #if defined(AM_TEST_KNOBS)
     if (getenv("AIRMODES_TRACE_SPEC")) fprintf(stderr, "airmodes: chain visit %s, %u blocks\n", fused ? "fused" : "separate", (M + 2047u) / 2048u);
 #endif
@@ -936,31 +944,25 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
         if (int rc = gate_prepare(c, n_max, n_ptr, c->pin_packets); rc != AM_OK) return rc;
     // extraction + slicing in one launch; the bursts and their tags leave the kernel only for the block-level
     // caller (am_preamble_work), the accepted packets always land in pinned host memory
-    c->pin_scalars[0] = 0;
-    c->pin_scalars[1] = cur0;
-    c->pin_scalars[2] = 0;
-    c->pin_scalars[5] = 0;
+    c->pin_scalars[AM_PW_HITS] = 0;
+    c->pin_scalars[AM_PW_RESUME] = cur0;
+    c->pin_scalars[AM_PW_CANDIDATES] = 0;
+    c->pin_scalars[AM_PW_CHAIN_ERR] = 0;
     // (the slicing waves write the accepted packets straight to the pinned array.  Routing them through device memory
     // and one coalesced copy in the ticket kernel was tried: the extraction kernel did not get faster and the copy
     // added 13 us to the ticket.)
+    am_slice_out so;
+    so.n_ptr = n_ptr; so.n_max = n_max; so.bursts_out = keep_dev ? c->bursts.p : nullptr; so.tags_out = keep_dev ? c->pin_tags : nullptr;
+    so.crc_pow = c->crc_pow.p; so.packets = c->pin_packets; so.scalars = c->scalars.p; so.host_out = c->pin_scalars; so.Mp = Mp;
+    so.fix_bits = c->fix_bits; so.gate = slice_gate(c, gate);
+    const am_stamp stamp = {base_abs, c->rate_i, c->tt_dev.p, (uint32_t)c->tt.size()};
     if (sc.sparse && !keep_bursts)
         // bb exists only around the candidates: the 240 soft chips of a hit are recomputed from the scan's samples
-        HIPCHK(c, am_launch_extract_slice_iq(sc.src, (long long)sc.src_abs0, (long long)sc.src_abs1,
-                                             c->use_pmf, c->s1, (const float *)c->inavg.p, c->spc,
-                                             (const uint4 *)c->emit_idx.p, n_ptr, n_max, (uint32_t *)c->pos.p,
-                                             (uint32_t *)c->e.p, base_abs, c->rate_i, (const am_time_tag *)c->tt_dev.p,
-                                             (uint32_t)c->tt.size(), keep_dev ? (float *)c->bursts.p : nullptr,
-                                             keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p,
-                                             c->pin_packets, (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp,
-                                             c->fix_bits, gate ? (c->ga.rl ? 2 : 1) : 0));
+        HIPCHK(c, am_launch_extract_slice_iq(recs, {sc.src, (long long)sc.src_abs0, (long long)sc.src_abs1, c->use_pmf, c->s1, c->spc},
+                                             c->emit_idx.p, stamp, so, c->stream));
     else
-    HIPCHK(c, am_launch_extract_slice(sc.ref.bb, (const float *)c->inavg.p, c->spc, c->frac ? (const int *)c->chip_idx.p : nullptr,
-                                      c->geom.hist0, (const uint4 *)c->emit_idx.p, n_ptr, n_max,
-                                      (uint32_t *)c->pos.p, (uint32_t *)c->e.p, base_abs, req.e_off, c->rate_i,
-                                      (const am_time_tag *)c->tt_dev.p, (uint32_t)c->tt.size(),
-                                      keep_dev ? (float *)c->bursts.p : nullptr,
-                                      keep_dev ? c->pin_tags : nullptr, (uint32_t *)c->crc_pow.p, c->pin_packets,
-                                      (uint32_t *)c->scalars.p, c->pin_scalars, c->stream, Mp, c->fix_bits, gate ? (c->ga.rl ? 2 : 1) : 0));
+        HIPCHK(c, am_launch_extract_slice(recs, {sc.ref.bb, c->frac ? c->chip_idx.p : nullptr, c->geom.hist0, req.e_off}, c->spc,
+                                          c->emit_idx.p, stamp, so, c->stream));
     if (gate) HIPCHK(c, am_launch_gate(c->ga, n_max, c->stream));     // behind the slicing launch, in front of the ticket
     if (req.copy_tail)
         // time shards: the samples the next step needs in front of its chunk, kept while this step's are still in place
@@ -968,10 +970,10 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
         HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
     const uint32_t seq = ++c->ticket_seq;
     if (gate)
-        HIPCHK(c, am_launch_gate_ticket(c->pin_scalars + 8, seq, c->ga.cnt, c->ga.rl, c->pin_scalars + 9, c->stream));
+        HIPCHK(c, am_launch_gate_ticket(c->pin_scalars, seq, c->ga.cnt, c->ga.rl, c->stream));
     else
-    HIPCHK(c, am_launch_ticket(c->pin_scalars + 8, seq, c->stream, req.flag_src, req.flag_src ? c->pin_scalars + 4 : nullptr,
-                               req.word_src, req.word_src ? reinterpret_cast<uint64_t *>(c->pin_scalars + 12) : nullptr));
+        HIPCHK(c, am_launch_ticket(c->pin_scalars + AM_PW_TICKET, seq, c->stream, req.flag_src, req.flag_src ? c->pin_scalars + AM_PW_FLAG : nullptr,
+                                   req.word_src, req.word_src ? reinterpret_cast<uint64_t *>(c->pin_scalars + AM_PW_EXIT) : nullptr));
     c->gate_live = gate;
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));          // end of the device work of this scan (behind the ticket)
     c->total_pending = true;
@@ -1098,6 +1100,18 @@ int hand_out_tags(am_ctx *c, float *bursts, am_tag *tags, uint64_t cap, uint64_t
     return AM_OK;
 }
 
+// From which messages the entry of the resident time chunk is composed, and where the composition leaves its results (scalars and
+// shard_exit exist)
+am_entry_src shard_entry_src(const am_ctx *c, const am_shard_exit *msgs, uint32_t world, uint32_t rank, uint32_t msg_cap)
+{
+    am_entry_src es;
+    es.msgs = msgs; es.world = world; es.rank = rank; es.cap = msg_cap;
+    es.base_abs = c->shard_base;
+    es.flags = c->scalars.p + AM_SW_ENTRY_FLAG;
+    es.exit_out = c->shard_exit.p;
+    return es;
+}
+
 // The resolve step of the resident time chunk: false if it has nothing to slice (no candidate, or the end-of-stream rule leaves
 // it no position that may emit); otherwise req is what its tail is asked for.  msgs (device): `world` exit tables of msg_cap
 // entries from which the walk composes the start position itself (scalars and shard_exit exist); null: the caller sets req.cur0.
@@ -1111,11 +1125,9 @@ bool resolve_plan(const am_ctx *c, const am_shard_exit *msgs, uint32_t world, ui
     req.max_hits = (uint32_t)((c->shard_end - c->shard_start + (uint64_t)c->spc) / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
     req.copy_tail = c->keep_bytes != 0;
     if (msgs) {
-        uint32_t *flag_dev = (uint32_t *)c->scalars.p + 5;
         req.has_entry = true;
-        req.entry.msgs = msgs; req.entry.world = world; req.entry.rank = rank; req.entry.cap = msg_cap;
-        req.entry.base_abs = c->shard_base; req.entry.flags = flag_dev; req.entry.exit_out = (uint64_t *)c->shard_exit.p;
-        req.flag_src = flag_dev;
+        req.entry = shard_entry_src(c, msgs, world, rank, msg_cap);
+        req.flag_src = req.entry.flags;
     }
     return true;
 }
@@ -1230,13 +1242,11 @@ void am_destroy(am_ctx *c)
                 c->ht_n, c->ht[0] / c->ht_n, c->ht[1] / c->ht_n, c->ht[2] / c->ht_n, c->ht[5] / c->ht_n, c->ht[3] / c->ht_n, c->ht[4] / c->ht_n, c->ht[6], c->ht[7] / c->ht_n);
 #endif
     (void)hipSetDevice(c->device);
-    DevBuf *all[] = {&c->raw_in, &c->pb_bb, &c->pb_avg, &c->bbmax, &c->carry, &c->carry2, &c->src, &c->bb, &c->avg, &c->cand_seg, &c->inavg, &c->dcount, &c->off_local, &c->blk_tot2, &c->blk_base2,
-                     &c->energy, &c->bits, &c->seg_base, &c->blk_cnt, &c->blk_off,
-                     &c->pos, &c->e, &c->tgt, &c->valid, &c->jump, &c->emit_idx,
-                     &c->lb_dc, &c->lb_mark, &c->lb_entry, &c->cblk_cnt, &c->cblk_off, &c->scalars, &c->bursts, &c->tags, &c->packets, &c->crc_pow,
-                     &c->recs, &c->cscratch, &c->dc_m1, &c->dc_y, &c->tt_dev, &c->wgmax, &c->shard_exit, &c->chip_idx,
-                     &c->gate_rec, &c->gate_scratch, &c->gate_map, &c->gate_multi, &c->gate_list};
-    for (DevBuf *b : all) release(*b);
+    release_all(c->raw_in, c->pb_bb, c->pb_avg, c->bbmax, c->carry, c->carry2, c->src, c->bb, c->avg, c->cand_seg, c->inavg, c->dcount, c->off_local,
+            c->blk_tot2, c->blk_base2, c->energy, c->bits, c->seg_base, c->blk_cnt, c->blk_off, c->pos, c->e, c->tgt, c->valid, c->jump,
+            c->emit_idx, c->lb_dc, c->lb_mark, c->lb_entry, c->cblk_cnt, c->cblk_off, c->scalars, c->bursts, c->tags, c->packets,
+            c->crc_pow, c->cscratch, c->dc_m1, c->dc_y, c->tt_dev, c->wgmax, c->shard_exit, c->chip_idx, c->gate_rec,
+            c->gate_scratch, c->gate_map, c->gate_multi, c->gate_list);
     if (c->pin_packets) (void)hipHostFree(c->pin_packets);
     if (c->pin_tags) (void)hipHostFree(c->pin_tags);
     if (c->pin_scalars) (void)hipHostFree(c->pin_scalars);
@@ -1373,7 +1383,7 @@ int am_get_address_gate_stats(const am_ctx *c, uint64_t *taught, uint64_t *passe
         unsigned long long v = 0;
         if (c->gate_map.p) {
             if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
-                hipMemcpy(&v, (const unsigned long long *)c->gate_map.p + 1, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+                hipMemcpy(&v, c->gate_map.p + 1, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
                 return AM_EHIP;
         }
         *not_learned = v;
@@ -1471,7 +1481,7 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         src = static_cast<const float *>(in);           // zero copy
     } else if (c->carry_n + n > 0) {
         ENSURE(c, c->src, (c->carry_n + n) * 2 * sizeof(float));
-        float *d = (float *)c->src.p;
+        float *d = c->src.p;
         if (c->carry_n) {
             HIPCHK(c, hipMemcpyAsync(d, c->carry.p, c->carry_n * 2 * sizeof(float), hipMemcpyDeviceToDevice,
                                      c->stream));
@@ -1501,11 +1511,11 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         const uint64_t pad = zero_pad(c->spc_hi);
         const bool generic = scan_path(c, false) == PATH_GENERIC;
         ENSURE(c, c->bb, (out_n + pad) * sizeof(float));
-        float *bb = (float *)c->bb.p, *avg = nullptr;
+        float *bb = c->bb.p, *avg = nullptr;
         ZERO_TAIL(c, 0, bb, out_n, pad);
         if (generic) {          // the fused kernel carries the reference level in the candidate records
             ENSURE(c, c->avg, (out_n + pad) * sizeof(float));
-            avg = (float *)c->avg.p;
+            avg = c->avg.p;
             ZERO_TAIL(c, 1, avg, out_n, pad);
         }
         const uint32_t j0 = (uint32_t)(P0 - out_abs0), j1 = (uint32_t)(P1 - out_abs0);
@@ -1833,14 +1843,14 @@ int am_frontend_work(am_ctx *c, const float *iq, uint64_t n, uint32_t flags, flo
     if (!(flags & AM_F_DEVICE_IN)) {
         ENSURE(c, c->src, n * 2 * sizeof(float));
         HIPCHK(c, hipMemcpyAsync(c->src.p, iq, n * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        src = (const float *)c->src.p;
+        src = c->src.p;
     }
     float *dbb = bb, *davg = avg;
     if (!(flags & AM_F_DEVICE_OUT)) {
         ENSURE(c, c->bb, n * sizeof(float));
         ENSURE(c, c->avg, n * sizeof(float));
-        dbb = (float *)c->bb.p;
-        davg = (float *)c->avg.p;
+        dbb = c->bb.p;
+        davg = c->avg.p;
     }
     uint64_t s0 = 0;
     int rc = apply_dcblock(c, &src, &s0, n, 0);
@@ -1872,7 +1882,7 @@ int am_preamble_work(am_ctx *c, const float *in, const float *inavg, uint64_t n,
     const uint64_t pad = zero_pad(c->spc_hi);
     ENSURE(c, c->bb, (n + pad) * sizeof(float));
     ENSURE(c, c->avg, (n + pad) * sizeof(float));
-    float *bb = (float *)c->bb.p, *avg = (float *)c->avg.p;
+    float *bb = c->bb.p, *avg = c->avg.p;
     const hipMemcpyKind kind = (flags & AM_F_DEVICE_IN) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     HIPCHK(c, hipMemcpyAsync(bb, in, n * sizeof(float), kind, c->stream));
     HIPCHK(c, hipMemcpyAsync(avg, inavg, n * sizeof(float), kind, c->stream));
@@ -1922,7 +1932,7 @@ int am_preamble_stream(am_ctx *c, const float *in, const float *inavg, uint64_t 
     if (nn) {
         ENSURE(c, c->bb, (nn + pad) * sizeof(float));
         ENSURE(c, c->avg, (nn + pad) * sizeof(float));
-        float *bb = (float *)c->bb.p, *avg = (float *)c->avg.p;
+        float *bb = c->bb.p, *avg = c->avg.p;
         if (c->pb_carry_n) {
             HIPCHK(c, hipMemcpyAsync(bb, c->pb_bb.p, c->pb_carry_n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(avg, c->pb_avg.p, c->pb_carry_n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -1996,15 +2006,17 @@ int am_slicer_work(am_ctx *c, const float *bursts, const am_tag *tags, uint64_t 
     HIPCHK(c, hipMemcpyAsync(c->tags.p, tags, nb * sizeof(am_tag), kind, c->stream));
     if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
     const uint32_t nb32 = (uint32_t)nb;
-    HIPCHK(c, hipMemcpyAsync(c->scalars.p, &nb32, sizeof(nb32), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->scalars.p + AM_SW_NBURSTS, &nb32, sizeof(nb32), hipMemcpyHostToDevice, c->stream));
     // the address gate on the block alone: the bursts are taken in the order given (item counts ascending, as the preamble block
     // emits them), nothing is ever repeated, so the call's teaches enter the map right behind its tests
     const bool gate = c->gate_mode != 0;
     if (gate)
-        if (int rc = gate_prepare(c, nb32, nullptr, (am_packet *)c->packets.p); rc != AM_OK) return rc;
-    HIPCHK(c, am_launch_slice((float *)c->bursts.p, (am_tag *)c->tags.p, (const uint32_t *)c->scalars.p, nb32,
-                              (uint32_t *)c->crc_pow.p, (am_packet *)c->packets.p, (const uint32_t *)c->scalars.p, nullptr,
-                              c->stream, nullptr, c->fix_bits, gate ? (c->ga.rl ? 2 : 1) : 0));
+        if (int rc = gate_prepare(c, nb32, nullptr, c->packets.p); rc != AM_OK) return rc;
+    am_slice_out so;
+    so.n_ptr = c->scalars.p + AM_SW_NBURSTS; so.n_max = nb32; so.bursts_out = nullptr; so.tags_out = nullptr;
+    so.crc_pow = c->crc_pow.p; so.packets = c->packets.p; so.scalars = c->scalars.p; so.host_out = nullptr; so.Mp = nullptr;
+    so.fix_bits = c->fix_bits; so.gate = slice_gate(c, gate);
+    HIPCHK(c, am_launch_slice(c->bursts.p, c->tags.p, so, c->stream));
     unsigned long long gcnt[3] = {0, 0, 0};
     uint32_t rcnt[2] = {0, 0};
     if (gate) {
@@ -2127,7 +2139,7 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
     if (!(flags & AM_F_DEVICE_IN) && nsrc) {
         ENSURE(c, c->src, nsrc * 2 * sizeof(float));
         HIPCHK(c, hipMemcpyAsync(c->src.p, iq, nsrc * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        src = (const float *)c->src.p;
+        src = c->src.p;
     }
     // positions this chunk owns; the global end-of-stream rule bounds the last chunk -- unless the stream goes on (AM_F_MORE:
     // total_n = samples so far; the chunk must come with its whole right halo)
@@ -2151,11 +2163,11 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
     if (P1 > P0 && out_n) {
         const bool generic = scan_path(c, false) == PATH_GENERIC;
         ENSURE(c, c->bb, (out_n + pad) * sizeof(float));
-        float *bb = (float *)c->bb.p, *avg = nullptr;
+        float *bb = c->bb.p, *avg = nullptr;
         ZERO_TAIL(c, 0, bb, out_n, pad);
         if (generic) {
             ENSURE(c, c->avg, (out_n + pad) * sizeof(float));
-            avg = (float *)c->avg.p;
+            avg = c->avg.p;
             ZERO_TAIL(c, 1, avg, out_n, pad);
         }
         int rc = run_front_and_candidates(c, src, fsrc_abs0, src_abs1, out_abs0, out_n, bb, avg,
@@ -2176,19 +2188,17 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
     if (msg_dev) {
         // host-free: the table (what fits the message) and its count go to the device message; whether the capacity
         // this scan was launched for sufficed comes back with the resolve step's completion ticket
-        const uint32_t M = sc.M, *Mp = sc.Mp;
+        const uint32_t M = sc.M;
         int rc = chain_prepare(c, true);
         if (rc != AM_OK) return rc;
         n_dev = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(M, lead + 1), msg_cap);
         if (int rce = ensure_shard_exit(c); rce != AM_OK) return rce;
         // the message header: {entries, overflow}, {where the scan left this chunk a step ago, -} -- written by the table kernel,
         // or (no candidate at all) by a one-wave launch
-        if (!n_dev) HIPCHK(c, am_launch_shard_header(msg_dev, (const uint64_t *)c->shard_exit.p, c->stream));
+        if (!n_dev) HIPCHK(c, am_launch_shard_header(msg_dev, c->shard_exit.p, c->stream));
         if (n_dev)
-            HIPCHK(c, am_launch_chain_exit_table((uint32_t *)c->pos.p, (uint32_t *)c->tgt.p, M, n_dev,
-                                                 (uint32_t)std::min<uint64_t>(lead_end - out_abs0, 0xFFFFFFFFull),
-                                                 (uint32_t *)c->cscratch.p, out_abs0, msg_dev + AM_SHARD_MSG_HEADER, c->stream, Mp,
-                                                 msg_dev, (const uint64_t *)c->shard_exit.p));
+            HIPCHK(c, am_launch_chain_exit_table(c->records(), n_dev, (uint32_t)std::min<uint64_t>(lead_end - out_abs0, 0xFFFFFFFFull),
+                                                 c->cscratch.p, out_abs0, {msg_dev + AM_SHARD_MSG_HEADER, msg_dev, c->shard_exit.p}, c->stream));
         c->last_M = M;
         c->shard_ready = true;
         return AM_OK;
@@ -2209,19 +2219,18 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
                                         hipHostMallocCoherent | hipHostMallocMapped));
                 c->pin_exit_cap = n_dev + 64;
             }
-            HIPCHK(c, am_launch_chain_exit_table((uint32_t *)c->pos.p, (uint32_t *)c->tgt.p, M, n_dev,
-                                                 (uint32_t)std::min<uint64_t>(lead_end - out_abs0, 0xFFFFFFFFull),
-                                                 (uint32_t *)c->cscratch.p, out_abs0, c->pin_exit, c->stream, Mp));
+            HIPCHK(c, am_launch_chain_exit_table(c->records(), n_dev, (uint32_t)std::min<uint64_t>(lead_end - out_abs0, 0xFFFFFFFFull),
+                                                 c->cscratch.p, out_abs0, {c->pin_exit, nullptr, nullptr}, c->stream));
         }
         // one completion ticket (with the device-side candidate count of a capacity launch) instead of
         // copies through the runtime and a stream synchronisation
-        c->pin_scalars[3] = M;
+        c->pin_scalars[AM_PW_SHARD_COUNT] = M;
         const uint32_t seq = ++c->ticket_seq;
-        HIPCHK(c, am_launch_ticket(c->pin_scalars + 8, seq, c->stream, Mp, c->pin_scalars + 3));
+        HIPCHK(c, am_launch_ticket(c->pin_scalars + AM_PW_TICKET, seq, c->stream, Mp, c->pin_scalars + AM_PW_SHARD_COUNT));
         HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
         c->total_pending = true;
         HIPCHK(c, wait_for_ticket(c, seq));
-        actual = c->pin_scalars[3];
+        actual = c->pin_scalars[AM_PW_SHARD_COUNT];
         if (!Mp || actual <= M) { c->last_M = actual; break; }
         // more candidates than the capacity this scan was launched for: once more with the exact count
 #if defined(AM_TEST_KNOBS)
@@ -2382,7 +2391,7 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
     c->pending.clear();
     c->last_tags = 0;
     if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
-    uint32_t *cur0_dev = (uint32_t *)c->scalars.p + 4, *flag_dev = (uint32_t *)c->scalars.p + 5;
+    uint32_t *cur0_dev = c->scalars.p + AM_SW_ENTRY, *flag_dev = c->scalars.p + AM_SW_ENTRY_FLAG;
     // the entry position of this chunk is composed from everybody's exit tables on the device: by the block walk itself, or
     // (nothing to slice here) by a launch of its own -- the other ranks must still learn whether a table overflowed: it did
     // so on every rank alike
@@ -2390,8 +2399,7 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
     if (int rce = ensure_shard_exit(c); rce != AM_OK) return rce;
     TailReq req;                                                // (entry.cur_in stays null: the scan position comes from the last rank's header)
     if (!resolve_plan(c, msgs_dev, world, rank, (uint32_t)msg_cap, req)) {
-        HIPCHK(c, am_launch_shard_entry(msgs_dev, world, rank, (uint32_t)msg_cap, c->shard_base, cur0_dev, flag_dev,
-                                        (uint64_t *)c->shard_exit.p, c->stream));
+        HIPCHK(c, am_launch_shard_entry(shard_entry_src(c, msgs_dev, world, rank, (uint32_t)msg_cap), cur0_dev, c->stream));
         uint32_t f = 0;
         if (c->keep_bytes) HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(&f, flag_dev, sizeof(f), hipMemcpyDeviceToHost, c->stream));
@@ -2406,7 +2414,7 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
     if (rc != AM_OK && rc != AM_RETRY_EXACT) { c->last_dom_ms = 0.0f; return rc; }
     read_dom_ms(c);
     if (rc == AM_RETRY_EXACT) { c->pending.clear(); *redo = 1; return AM_OK; }   // more candidates than the capacity the scan was launched for
-    if (c->pin_scalars[4]) { c->pending.clear(); *redo = 1; return AM_OK; }       // a table did not fit its message
+    if (c->pin_scalars[AM_PW_FLAG]) { c->pending.clear(); *redo = 1; return AM_OK; }       // a table did not fit its message
     note_density(c, c->shard_end - c->shard_start);
     c->last_tags = c->n_hits;
     return hand_out(c, out, cap, n_out);
@@ -2481,25 +2489,26 @@ static int shard_resolve_enqueue(am_ctx *c, const am_shard_exit *msgs, uint32_t 
     c->last_tags = 0;
     if (int rcs = ensure_scalars(c); rcs != AM_OK) return rcs;
     if (int rce = ensure_shard_exit(c); rce != AM_OK) return rce;
-    uint32_t *cur0_dev = (uint32_t *)c->scalars.p + 4, *flag_dev = (uint32_t *)c->scalars.p + 5;
+    uint32_t *cur0_dev = c->scalars.p + AM_SW_ENTRY, *flag_dev = c->scalars.p + AM_SW_ENTRY_FLAG;
     if (int rcp = ensure_pin_scalars(c); rcp != AM_OK) return rcp;
     am_ctx::Pending &P = c->pend;
     P = am_ctx::Pending();
     TailReq req;
     if (!resolve_plan(c, msgs, world, rank, msg_cap, req)) {
         // nothing to slice: the entry is still composed (the chunk passes the scan position on), one ticket
-        HIPCHK(c, am_launch_shard_entry(msgs, world, rank, msg_cap, c->shard_base, cur0_dev, flag_dev, (uint64_t *)c->shard_exit.p, c->stream, cur_in,
-                                        carry_out));
+        am_entry_src es = shard_entry_src(c, msgs, world, rank, msg_cap);
+        es.cur_in = cur_in; es.carry_out = carry_out;
+        HIPCHK(c, am_launch_shard_entry(es, cur0_dev, c->stream));
         if (walk_done) HIPCHK(c, hipEventRecord(walk_done, c->stream));
         if (c->keep_bytes) HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
         const uint32_t seq = ++c->ticket_seq;
-        HIPCHK(c, am_launch_ticket(c->pin_scalars + 8, seq, c->stream, flag_dev, c->pin_scalars + 4, (const uint64_t *)c->shard_exit.p,
-                                   reinterpret_cast<uint64_t *>(c->pin_scalars + 12)));
+        HIPCHK(c, am_launch_ticket(c->pin_scalars + AM_PW_TICKET, seq, c->stream, flag_dev, c->pin_scalars + AM_PW_FLAG, c->shard_exit.p,
+                                   reinterpret_cast<uint64_t *>(c->pin_scalars + AM_PW_EXIT)));
         P.active = true; P.scanned = false; P.seq = seq;
         return AM_OK;
     }
     req.entry.cur_in = cur_in; req.entry.carry_out = carry_out;
-    req.word_src = (const uint64_t *)c->shard_exit.p;
+    req.word_src = c->shard_exit.p;
     req.walk_event = walk_done;
     req.defer = true;
     uint32_t fin = 0;
@@ -2527,9 +2536,9 @@ static int shard_resolve_complete(am_ctx *c, int *redo, uint64_t *exit_after)
         c->tail_synced = true;
     P.active = false; P.scanned = false;
     if (rc != AM_OK) return rc;
-    if (c->pin_scalars[4]) *redo = 1;                           // (the header said so)
+    if (c->pin_scalars[AM_PW_FLAG]) *redo = 1;                           // (the header said so)
     if (*redo) c->pending.clear();
-    if (exit_after) *exit_after = *reinterpret_cast<volatile uint64_t *>(c->pin_scalars + 12);
+    if (exit_after) *exit_after = *reinterpret_cast<volatile uint64_t *>(c->pin_scalars + AM_PW_EXIT);
     note_density(c, c->shard_end - c->shard_start);
     c->last_tags = c->n_hits;
     read_dom_ms(c);
@@ -2559,7 +2568,7 @@ static int spipe_enqueue(am_spipe *p, size_t k)
     if (!sl.first && p->prev_slot >= 0) {
         am_spipe_slot &pv = p->slot[(size_t)p->prev_slot];
         if (int rce = ensure_shard_exit(pv.c); rce != AM_OK) return rce;
-        cur_in = (const uint64_t *)pv.c->shard_exit.p;
+        cur_in = pv.c->shard_exit.p;
         HIPCHK(c, hipStreamWaitEvent(c->stream, pv.done, 0));
     }
     return shard_resolve_enqueue(c, sl.msg, 1, 0, p->msg_cap, cur_in, nullptr, sl.done);

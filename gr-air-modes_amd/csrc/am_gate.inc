@@ -241,26 +241,29 @@ __global__ void __launch_bounds__(256) am_k_gate_commit(am_gate_args a)
     atomicAdd(&a.t_hdr[1], 1ull);
 }
 
-// am_k_ticket for a scan with the gate: the call's counters (taught, passed, dropped) travel with the ticket
+// am_k_ticket for a scan with the gate: the call's counters (taught, passed, dropped) travel with the ticket.
+// cnt_dst = the context's pinned block from AM_PW_GATE_TAUGHT on
+#define AM_GATE_DST(word) ((word) - AM_PW_GATE_TAUGHT)
 __global__ void am_k_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, uint32_t *cnt_dst)
 {
-    cnt_dst[0] = (uint32_t)cnt[0];
-    cnt_dst[1] = (uint32_t)cnt[1];
-    cnt_dst[2] = (uint32_t)cnt[2];
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_TAUGHT)] = (uint32_t)cnt[0];
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_PASSED)] = (uint32_t)cnt[1];
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_DROPPED)] = (uint32_t)cnt[2];
     __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// ... and with the repair on, two more: repaired, ambiguous (cnt_dst[5], [6])
+// ... and with the repair on, two more: repaired, ambiguous
 __global__ void am_k_gate_repair_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl,
                                         uint32_t *cnt_dst)
 {
-    cnt_dst[0] = (uint32_t)cnt[0];
-    cnt_dst[1] = (uint32_t)cnt[1];
-    cnt_dst[2] = (uint32_t)cnt[2];
-    cnt_dst[5] = rl[1];
-    cnt_dst[6] = rl[2];
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_TAUGHT)] = (uint32_t)cnt[0];
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_PASSED)] = (uint32_t)cnt[1];
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_DROPPED)] = (uint32_t)cnt[2];
+    cnt_dst[AM_GATE_DST(AM_PW_REPAIRED)] = rl[1];
+    cnt_dst[AM_GATE_DST(AM_PW_AMBIGUOUS)] = rl[2];
     __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+#undef AM_GATE_DST
 
 size_t am_gate_scratch_bytes(uint32_t slots) { return ((size_t)4 + (size_t)3 * slots) * sizeof(unsigned long long); }
 
@@ -298,9 +301,9 @@ hipError_t am_launch_gate_commit(const am_gate_args &a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t am_launch_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl,
-                                 uint32_t *cnt_dst, hipStream_t s)
+hipError_t am_launch_gate_ticket(uint32_t *pin, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl, hipStream_t s)
 {
+    uint32_t *host_word = pin + AM_PW_TICKET, *cnt_dst = pin + AM_PW_GATE_TAUGHT;
     if (rl) hipLaunchKernelGGL(am_k_gate_repair_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, rl, cnt_dst);
     else hipLaunchKernelGGL(am_k_gate_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, cnt_dst);
     return hipGetLastError();

@@ -1,11 +1,25 @@
 // am_internal.h -- kernel launch interface between am_capi.hip (host logic) and the gfx950 kernels with their launchers:
 // am_kernels.hip, am_fe2.hip (test builds), am_fe3.hip, am_fe4.hip, am_refine_seg.hip, am_dcblock.hip, am_resample.hip.
 // Not part of the public ABI.
+//
+// How a launcher is called: what several launches share travels as one small struct, built where the context knows it --
+//   am_records      the resident candidate records and their count (every refinement, the chain, the extraction)
+//   am_emit_args    what the chain does with the candidates it visits; the marking kernels take it by value
+//   am_slice_out    what a slicing launch writes and which <FIX, GATE> instantiation runs (all three slicing launches)
+//   am_stamp        the time tags of the two extraction launches
+// -- and a launcher has a struct of its own only for what is its alone (am_walk_req, am_dense_src, am_iq_src, ...).  A launcher that
+// takes one of them has no default arguments: an option nobody wants is written out as null or 0 at the call.  The launchers unpack the
+// structs into kernel arguments; no __global__ function's parameter list depends on them, except where it always did
+// (am_emit_args, am_entry_src, am_fe_args, am_geom).  The words of the context's two scalar blocks have names
+// (am_scalar_word, am_pinned_word) that host and kernels share; which template instantiation a run-time value selects is
+// decided in am_dispatch.h.
 #ifndef AM_INTERNAL_H
 #define AM_INTERNAL_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <initializer_list>
 
 #include "airmodes_hip.h"
 #include "airmodes_hip_debug.h"
@@ -18,6 +32,56 @@
 #define AM_WAVE 64
 
 int am_device_cus(void);   /* compute units of the current device (cached)                  */
+
+/* ---- the two scalar blocks of a context ------------------------------------------------------
+ * Every context has a small block of 32-bit words in device memory (`scalars`, zero when allocated) and one in pinned host
+ * memory (`pin_scalars`) that the last kernels of a scan write for the host.  Host and kernels address both by these names only. */
+enum am_scalar_word {            /* device block */
+    AM_SW_RESUME = 0,            /* where the greedy scan resumes: cleared by am_k_cblk_exit, raised by the walk and the marking  */
+    AM_SW_NBURSTS = AM_SW_RESUME,/* INTENDED ALIAS: am_slicer_work, which runs no chain, keeps its burst count (n_ptr) here       */
+    AM_SW_HIT = 1,               /* cleared with AM_SW_RESUME                                                                     */
+    AM_SW_ENTRY = 4,             /* time shards: the array coordinate at which the scan enters the chunk (am_k_shard_entry)       */
+    AM_SW_ENTRY_FLAG = 5,        /* ... 1: some exit table did not fit its message, the step is repeated                          */
+    AM_SW_CHAIN_ERR = 9,         /* a chained scan or the fused walk gave up waiting (am_chain_prefix, am_cblk_mark_body)         */
+    AM_SW_TICKET_SCAN = 10,      /* ticket counter of am_k_exscan_chain (am_chain_place)                                          */
+    AM_SW_TICKET_MARK = 11,      /* ... of the marking kernels                                                                    */
+    AM_SW_GATE_REC = 14,         /* 64 bits, words 14..15: the address of the gate's record array (am_slice_wave<FIX, 1 or 2>)    */
+    AM_SW_WORDS = 16
+};
+enum am_pinned_word {            /* pinned block */
+    AM_PW_HITS = 0,              /* the slicing launch: hits, ...                                                                 */
+    AM_PW_RESUME = 1,            /* ... scalars[AM_SW_RESUME], ...                                                                */
+    AM_PW_CANDIDATES = 2,        /* ... *Mp, the candidate count of a capacity launch (0 without one)                             */
+    AM_PW_SHARD_COUNT = 3,       /* am_shard_scan's ticket: the same count, before any tail runs                                  */
+    AM_PW_FLAG = 4,              /* a time shard's ticket: scalars[AM_SW_ENTRY_FLAG]                                              */
+    AM_PW_CHAIN_ERR = 5,         /* the extraction launches: scalars[AM_SW_CHAIN_ERR]                                             */
+    AM_PW_TICKET = 8,            /* the completion ticket the host polls (wait_for_ticket)                                        */
+    AM_PW_GATE_TAUGHT = 9,       /* am_k_gate_ticket: taught, ...                                                                 */
+    AM_PW_GATE_PASSED = 10,      /* ... passed, ...                                                                               */
+    AM_PW_GATE_DROPPED = 11,     /* ... dropped                                                                                   */
+    AM_PW_EXIT = 12,             /* 64 bits, words 12..13: where the scan left a time chunk (am_k_ticket's word_dst)              */
+    AM_PW_REPAIRED = 14,         /* am_k_gate_repair_ticket: address/parity replies repaired, ...                                 */
+    AM_PW_AMBIGUOUS = 15,        /* ... and left alone because two addresses fitted                                               */
+    AM_PW_WORDS = 16
+};
+/* (AM_SW_NBURSTS above is the only alias; every other name of a block has a word, or an aligned pair of words, to itself) */
+constexpr bool am_word_map_ok(std::initializer_list<int> words, int size)   /* every word inside the block, no word twice */
+{
+    for (const int *a = words.begin(); a != words.end(); ++a) {
+        if (*a < 0 || *a >= size) return false;
+        for (const int *b = words.begin(); b != a; ++b)
+            if (*a == *b) return false;
+    }
+    return true;
+}
+static_assert(am_word_map_ok({AM_SW_RESUME, AM_SW_HIT, AM_SW_ENTRY, AM_SW_ENTRY_FLAG, AM_SW_CHAIN_ERR, AM_SW_TICKET_SCAN,
+                              AM_SW_TICKET_MARK, AM_SW_GATE_REC, AM_SW_GATE_REC + 1}, AM_SW_WORDS), "device block");
+static_assert(am_word_map_ok({AM_PW_HITS, AM_PW_RESUME, AM_PW_CANDIDATES, AM_PW_SHARD_COUNT, AM_PW_FLAG, AM_PW_CHAIN_ERR,
+                              AM_PW_TICKET, AM_PW_GATE_TAUGHT, AM_PW_GATE_PASSED, AM_PW_GATE_DROPPED, AM_PW_EXIT, AM_PW_EXIT + 1,
+                              AM_PW_REPAIRED, AM_PW_AMBIGUOUS}, AM_PW_WORDS), "pinned block");
+static_assert(AM_SW_GATE_REC % 2 == 0 && AM_PW_EXIT % 2 == 0, "the 64-bit slots are 8-byte aligned (the blocks themselves are)");
+static_assert(AM_PW_GATE_PASSED == AM_PW_GATE_TAUGHT + 1 && AM_PW_GATE_DROPPED == AM_PW_GATE_TAUGHT + 2,
+              "the gate's three counters are consecutive (chain_collect adds them up in a loop)");
 
 /* Geometry of the preamble block for one sample rate, in the reference's own arithmetic: d_samples_per_chip is a FLOAT
  * (lib/preamble_impl.cc:57) and every use of it is a float product truncated by int() -- for a rate that is not a multiple
@@ -33,6 +97,30 @@ struct am_geom {
     int B;              /* items consume_each() skips after a hit: int(240 spc) (:237)                               */
     int room;           /* a hit needs `ninputs - i < 240 spc` to be false (:212): at least this many items          */
     int span;           /* int(239 spc): offset of the last soft chip (:220)                                         */
+};
+
+/* ---- the resident records ----------------------------------------------------------------
+ * One flat record per candidate, in position order: what a refinement writes and the greedy chain and the extraction read.
+ * The context builds the struct in one place (am_ctx::records); every launcher takes it as `const am_records &` -- the
+ * pointers are not const because the refinements write through them -- and unpacks it into its kernel's arguments.
+ * M is the number of records, or the capacity they were launched for when the count is only known on the device: then
+ * Mp points at it and the kernels use min(M, *Mp), so that the host may launch without knowing the count. */
+struct am_records {
+    uint32_t *pos;         /* position where the first-stage test fired                                   */
+    uint32_t *e;           /* shifted preamble start                                                      */
+    uint32_t *tgt;         /* where the scan resumes after this candidate                                 */
+    float *inavg;          /* reference level at e                                                        */
+    uint8_t *valid;
+    uint32_t *jump0;       /* M + 1 successors of the greedy chain (null where no launch reads them)      */
+    uint32_t M;
+    const uint32_t *Mp;    /* null: M is exact                                                            */
+};
+/* what the refinements behind a front end read: bb (dense, or the rows around candidates), the reference level (likewise),
+ * the threshold, and the first array coordinate without a sample */
+struct am_refine_in {
+    const float *bb, *avg;
+    float thr_lin;
+    uint32_t end_j;
 };
 
 /* ---- front end ---------------------------------------------------------------------- */
@@ -117,6 +205,11 @@ struct am_fe_stream_req {
     uint32_t *bits, *wg_cnt;
     float *wg_max;
 };
+/* ... and what it left, for the kernels that read it */
+struct am_fe_marks {
+    const uint32_t *bits, *wg_cnt;
+    const float *wg_max;
+};
 /* *layout: what was launched (nsteps == 0: nothing).  wgs_per_cu: 0 = as many persistent workgroups as are resident at once;
  * n > 0 = at most n per CU -- am_pipe leaves room on every CU for the small kernels of the other batches in flight. */
 hipError_t am_launch_fe3(const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu, bool levelled);
@@ -143,10 +236,8 @@ hipError_t am_launch_gather_wg(const uint32_t *bits, const uint32_t *wg_cnt, con
  * (am_refine_seg.hip): what am_launch_gather_wg(rows) + am_launch_refine_late(bb_max) leave in pos / e / tgt / inavg / valid / jump0,
  * bit for bit, without the bb rows ever reaching memory.  rows: the samples (bb_sparse / bb_max are not used).  Places the
  * layout's two segment lengths. */
-hipError_t am_launch_refine_seg(const uint32_t *bits, const uint32_t *wg_cnt, const float *wg_max, const am_fe_layout &l, uint32_t Mcap,
-                                const am_rows_args &rows, const float *avg_sparse, float thr_lin, uint32_t end_j, uint32_t *pos,
-                                uint32_t *e, uint32_t *tgt, float *inavg, uint8_t *valid, uint32_t *jump0, uint32_t *total_out,
-                                hipStream_t s);
+hipError_t am_launch_refine_seg(const am_fe_marks &m, const am_fe_layout &l, const am_rows_args &rows, const am_refine_in &in,
+                                const am_records &r, uint32_t *total_out, hipStream_t s);   /* (in.bb is not read; r.M: the capacity) */
 /* split refinement (after the fused kernel in split mode): flat candidate positions, one energy per
  * reachable position (deduplicated across neighbouring candidates), then one lane per candidate */
 hipError_t am_launch_gather_pos(const uint32_t *seg_pos, uint32_t seg_stride, const uint32_t *blk_off,
@@ -155,18 +246,15 @@ hipError_t am_launch_gather_pos(const uint32_t *seg_pos, uint32_t seg_stride, co
 hipError_t am_launch_energy(const float *bb, const uint32_t *pos, const uint32_t *dcount,
                             const uint32_t *off_local, const uint32_t *blk_base, uint32_t M, int spc,
                             double *energy, hipStream_t s, const uint32_t *Mp = nullptr);
-hipError_t am_launch_cand(const float *bb, const float *avg_sparse, const uint32_t *pos, const uint32_t *dcount,
-                          const uint32_t *off_local, const uint32_t *blk_base, const double *energy, uint32_t M,
-                          int spc, float thr_lin, uint32_t end_j, uint32_t *e, uint32_t *tgt, float *inavg,
-                          uint8_t *valid, uint32_t *jump0, hipStream_t s, const uint32_t *Mp = nullptr);
+hipError_t am_launch_cand(const am_refine_in &in, const uint32_t *dcount, const uint32_t *off_local, const uint32_t *blk_base,
+                          const double *energy, int spc, const am_records &r, hipStream_t s);   /* (r.pos is read, the rest written) */
 /* behind the streaming front ends: late-peak decisions + per-candidate test + record + successor in one launch (the
- * decisions stay in LDS; no dcount / compact offsets).  vmax[array coordinate / l.vspan()] (l.nv() entries) bounds the samples */
-hipError_t am_launch_refine_late(const float *bb, const float *avg_sparse, const uint32_t *pos, uint32_t M, int spc,
-                                 float thr_lin, uint32_t end_j, uint32_t *e, uint32_t *tgt, float *inavg, uint8_t *valid,
-                                 uint32_t *jump0, hipStream_t s, const uint32_t *Mp, const float *vmax, const am_fe_layout &l,
-                                 const float *bb_max = nullptr);
-/* (bb_max, 32 samples per chip only: bb_max[c] = the largest bb of array chip c for every chip whose row exists -- am_k_gather_wg<1>
- * writes it with the rows; a quiet zone's whole chips are then judged by six numbers instead of 192 samples) */
+ * decisions stay in LDS; no dcount / compact offsets).  r.pos is read, the rest of r written.
+ * vmax[array coordinate / l.vspan()] (l.nv() entries) bounds the samples */
+hipError_t am_launch_refine_late(const am_refine_in &in, int spc, const am_records &r, const float *vmax, const am_fe_layout &l,
+                                 const float *bb_max, hipStream_t s);
+/* (bb_max, 32 samples per chip only, null elsewhere: bb_max[c] = the largest bb of array chip c for every chip whose row exists --
+ * am_k_gather_wg<1> writes it with the rows; a quiet zone's whole chips are then judged by six numbers instead of 192 samples) */
 /* exclusive scan of n counts in ONE launch (2048 per workgroup, chained through slots[]: am_chain_prefix);
  * slots: one 64-bit word per workgroup, zero at allocation; epoch: a value no earlier launch on these slots used */
 hipError_t am_launch_exscan_chain(const uint32_t *in, uint32_t *out, uint32_t n, unsigned long long *slots, uint32_t epoch,
@@ -186,47 +274,25 @@ hipError_t am_launch_dcblock(const float *raw, long long raw_abs0, long long raw
  * component) -> 2 n floats at out (device, 8-byte aligned) */
 hipError_t am_launch_unpack(int fmt, const void *raw, uint64_t n, float *out, hipStream_t s);
 
-/* Launchers that take a candidate count M also take an optional device pointer Mp: when given, the
- * kernels use min(M, *Mp), so that the host may launch for a capacity without knowing the count. */
 /* ---- preamble detection / refinement / greedy chain ----------------------------------- */
 #define AM_DET_THREADS 256
 #define AM_DET_PER_THREAD 8
 #define AM_DET_PER_BLOCK (AM_DET_THREADS * AM_DET_PER_THREAD)
-
-struct am_scan_buffers {
-    /* per detect block */
-    uint32_t *cand_seg;    /* nblk * AM_DET_PER_BLOCK candidate positions (segmented)       */
-    uint32_t *blk_cnt;     /* nblk                                                          */
-    uint32_t *blk_off;     /* nblk + 1 (exclusive scan, last = total)                       */
-    /* per candidate (flat, position order) */
-    uint32_t *pos;         /* position where the first-stage test fired                     */
-    uint32_t *e;           /* shifted preamble start                                        */
-    uint32_t *tgt;         /* where the scan resumes after this candidate                   */
-    uint8_t *valid;
-    uint8_t *visited;
-    uint8_t *emit;
-    uint32_t *jump;        /* (levels+1) * (M+1) pointer-doubling tables                    */
-    uint32_t *emit_idx;    /* compacted indices of emitted candidates                       */
-    uint32_t *cblk_cnt;    /* compaction block counts / offsets                             */
-    uint32_t *cblk_off;
-    uint32_t *scalars;     /* [0] = final scan position, [1] = visited&valid count          */
-};
 
 hipError_t am_launch_detect(const float *bb, const float *avg, uint32_t j0, uint32_t j1, const am_geom &g,
                             float thr_lin, uint32_t *cand_seg, uint32_t *blk_cnt, uint32_t nblk,
                             hipStream_t s);
 /* exclusive scan of n counts into off[0..n]; off[n] = total */
 hipError_t am_launch_scan_u32(const uint32_t *cnt, uint32_t *off, uint32_t n, hipStream_t s);
-hipError_t am_launch_refine(const float *bb, const float *avg, const am_geom &g, float thr_lin,
-                            const uint32_t *cand_seg, uint32_t seg_stride, const uint32_t *blk_off,
-                            uint32_t nblk, uint32_t M, uint32_t *pos, uint32_t *e, uint32_t *tgt,
-                            float *inavg, uint8_t *valid, hipStream_t s);
+/* (in.end_j is not read; r.M exact, r.jump0 not written) */
+hipError_t am_launch_refine(const am_refine_in &in, const am_geom &g, const uint32_t *cand_seg, uint32_t seg_stride,
+                            const uint32_t *blk_off, uint32_t nblk, const am_records &r, hipStream_t s);
 /* greedy chain (am_kernels.hip): step 1 is independent of where the scan starts */
 size_t am_chain_scratch_bytes(uint32_t M);
-hipError_t am_launch_chain_prepare(const uint32_t *pos, const uint32_t *tgt, uint32_t M, uint32_t *jump0,
-                                   uint32_t *scratch, int want_last, hipStream_t s, const uint32_t *Mp = nullptr,
-                                   int have_succ = 0, uint32_t *scalars = nullptr);   /* have_succ: jump0[] was written by am_k_cand;
-                                   scalars: its words [0 .. 1] are cleared (what the one-launch form of am_launch_chain_visit starts from) */
+/* have_succ: r.jump0[] was written by the refinement; scalars (or null): its words AM_SW_RESUME and AM_SW_HIT are cleared (what
+ * the one-launch form of am_launch_chain_visit starts from) */
+hipError_t am_launch_chain_prepare(const am_records &r, uint32_t *scratch, int want_last, int have_succ, uint32_t *scalars,
+                                   hipStream_t s);
 /* where the greedy scan of a time shard starts: composed on the device from everybody's exit tables (am_k_cblk_walk) */
 struct am_entry_src {
     const am_shard_exit *msgs = nullptr;      // null: the start position comes from the host
@@ -238,29 +304,55 @@ struct am_entry_src {
     const uint64_t *cur_in = nullptr;   // non-null: where the scan left the chunk BEFORE this one, read when the entry is composed (am_spipe)
 };
 
+/* What the scan does with the candidates it visits (preamble_impl.cc:209-237).  The marking kernels take this struct BY VALUE: its
+ * layout is part of their signature.  The caller of am_launch_chain_visit fills everything but the record pointers and
+ * ticket_base, which the launcher sets from its am_records and from *ticket_base. */
+struct am_emit_args {
+    const uint8_t *valid;
+    const uint32_t *pos, *e, *tgt;
+    const float *inavg;             // reference level of every candidate (goes into the hit records)
+    uint32_t emit_max;              // room rule (:212): a valid hit too close to the end of the stream is not
+                                    // emitted (and nothing after it can be)
+    uint32_t own_lo, own_hi;        // first-stage positions this GPU's time chunk owns (everything on one GPU)
+    uint4 *emit_idx;                // out: the candidates to extract, in position order: {candidate index, first-stage position,
+                                    // refined position, reference level (bits)} -- everything the extraction kernels need of a hit
+                                    // in ONE load (round 5: index -> e / inavg / pos was a dependent memory round trip per hit)
+    uint32_t *n_out;                // out: how many
+    unsigned long long *slots;      // chained scan of the per-block hit counts (am_chain_prefix)
+    uint32_t epoch;
+    uint32_t *ticket;               // ... and the counter its places are drawn from (am_chain_place)
+    uint32_t ticket_base;
+    uint32_t *scalars;              // [AM_SW_RESUME]: raised to the largest resume target of a visited candidate
+    int want_resume;
+};
 enum { AM_WALK_AUTO = 0, AM_WALK_SEPARATE = 1, AM_WALK_FUSED = 2 };   /* walk_mode: test builds force a form (AIRMODES_WALK) */
-hipError_t am_launch_chain_visit(const uint32_t *pos, const uint32_t *jump0, uint32_t M, uint32_t cur0,
-                                 uint32_t *scratch, const uint8_t *valid, const uint32_t *e, const uint32_t *tgt,
-                                 uint32_t emit_max, uint32_t own_lo, uint32_t own_hi, uint4 *emit_idx, uint32_t *n_out,
-                                 unsigned long long *slots, uint32_t epoch, uint32_t *ticket, uint32_t *ticket_base,
-                                 uint32_t *scalars, int want_resume,
-                                 hipStream_t s, const uint32_t *Mp, const am_entry_src *entry_src, const float *inavg,
-                                 hipEvent_t after_walk = nullptr, unsigned long long *entry_slots = nullptr,
-                                 int walk_mode = AM_WALK_AUTO, int *fused_out = nullptr);
-/* (entry_slots: one 64-bit word per block, zero at allocation, tagged with `epoch` like slots -- given, and with neither an entry
- * source nor a walk event, walk and marking are ONE launch whenever its workgroups are resident at once; null: two launches) */
-/* (emit_idx: one 16-byte record per hit -- candidate index, first-stage position, refined position, reference level -- so that
- * the extraction kernels fetch a hit with one load) */
+/* ... and what the walk in front of the marking is asked for */
+struct am_walk_req {
+    uint32_t cur0;                      /* where the scan starts (array coordinate), unless entry_src composes it                  */
+    uint32_t *scratch;                  /* am_chain_scratch_bytes(M), as am_launch_chain_prepare left it                            */
+    const am_entry_src *entry_src;      /* or null                                                                                  */
+    hipEvent_t after_walk;              /* or null: recorded behind the walk's launch                                               */
+    unsigned long long *entry_slots;    /* one 64-bit word per block, zero at allocation, tagged with ea.epoch like ea.slots -- given,
+                                           and with neither an entry source nor a walk event, walk and marking are ONE launch whenever
+                                           its workgroups are resident at once; null: two launches                                  */
+    int walk_mode;
+};
+/* *ticket_base: the value ea.ticket has when this launch starts (advanced by the grid size); *fused_out (or null): which form ran */
+hipError_t am_launch_chain_visit(const am_records &r, const am_emit_args &ea, const am_walk_req &w, uint32_t *ticket_base,
+                                 int *fused_out, hipStream_t s);
+/* exit table of a time chunk.  header (or null): the message header in front of the table, header[1] = {*carry, 0}: where the scan
+ * left this chunk a step ago */
+struct am_exit_dst {
+    am_shard_exit *table;
+    am_shard_exit *header;
+    const uint64_t *carry;
+};
 /* lead_end (array coordinate): the table is only needed up to the first candidate at or past it */
-hipError_t am_launch_chain_exit_table(const uint32_t *pos, const uint32_t *tgt, uint32_t M, uint32_t n,
-                                      uint32_t lead_end, uint32_t *scratch, uint64_t base_abs, am_shard_exit *table,
-                                      hipStream_t s, const uint32_t *Mp = nullptr, am_shard_exit *header = nullptr,
-                                      const uint64_t *carry = nullptr);   /* header[1] = {*carry, 0}: where the scan left this chunk a step ago */
-/* device-side am_shard_entry2: `world` messages of AM_SHARD_MSG_HEADER + cap entries; writes the array coordinate at which the
- * scan enters chunk `rank`, the absolute position at which it leaves it, and sets flags[0] if some table did not fit */
-hipError_t am_launch_shard_entry(const am_shard_exit *msgs, uint32_t world, uint32_t rank, uint32_t cap, uint64_t base_abs,
-                                 uint32_t *cur0_out, uint32_t *flags, uint64_t *exit_out, hipStream_t s, const uint64_t *cur_in = nullptr,
-                                 uint64_t *carry_out = nullptr);
+hipError_t am_launch_chain_exit_table(const am_records &r, uint32_t n, uint32_t lead_end, uint32_t *scratch, uint64_t base_abs,
+                                      const am_exit_dst &dst, hipStream_t s);
+/* device-side am_shard_entry2: es.world messages of AM_SHARD_MSG_HEADER + es.cap entries; writes the array coordinate at which the
+ * scan enters chunk es.rank (cur0_out), the absolute position at which it leaves it, and sets es.flags[0] if some table did not fit */
+hipError_t am_launch_shard_entry(const am_entry_src &es, uint32_t *cur0_out, hipStream_t s);
 /* the header of a message without a table: {0, 0}, {*carry, 0} */
 hipError_t am_launch_shard_header(am_shard_exit *header, const uint64_t *carry, hipStream_t s);
 
@@ -273,26 +365,61 @@ struct am_time_tag {
     double frac;
 };
 #define AM_MAX_TIME_TAGS 4096
-/* extraction + slicing of the emitted preambles in one launch.  n_ptr: device-side number of hits; n_max:
- * upper bound used for the grid; tt[0..ntt): device array of time tags in ascending offset order;
- * bursts_out / tags_out may be null */
-/* chip_idx: device table of the 240 soft chips' sample offsets int(j * samples per chip) (null: j * spc); hist0: history
- * items of the preamble block (the tag's item count = stream index + hist0) */
-hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc, const int *chip_idx, int hist0,
-                                   const uint4 *emit_idx,
-                                   const uint32_t *n_ptr, uint32_t n_max, const uint32_t *pos, const uint32_t *e,
-                                   uint64_t base_abs, long long e_off, uint64_t rate, const am_time_tag *tt,
-                                   uint32_t ntt, float *bursts_out, am_tag *tags_out, const uint32_t *crc_pow,
-                                   am_packet *packets, const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                   const uint32_t *Mp, int fix_bits, int gate);
+/* What the three slicing launches write, and which instantiation runs.  packets[i].reserved[0] = 1 when the reference would post
+ * the message, else 0.
+ * fix_bits: which instantiation am_k_*<FIX> runs -- 0 = the kernels as they are without the repair; 1, 2 = DF11 / DF17 replies with
+ * up to that many wrong bits are repaired (am_set_fix_errors) and the number flipped is left in reserved[1].
+ * gate: 1 = am_k_*<FIX, 1>, which also leaves an am_gate_rec per hit at the address in scalars[AM_SW_GATE_REC] (scalars must not be
+ * null then); 2 = am_k_*<FIX, 2>: the same, and an address/parity record carries its DF (am_k_gate_repair); 0 = the kernels as they
+ * are without the gate.
+ * NO MEMBER HAS AN INITIALISER, and no site value-initialises one of these ("am_slice_out o = {};"): a silent 0 in fix_bits or
+ * gate would run a scan without the repair and nobody would notice.  Each of the two sites that build one (chain_finish,
+ * am_slicer_work) assigns all eleven members by name, in this order, so that a missing one shows when the site is read. */
+struct am_slice_out {
+    const uint32_t *n_ptr;     /* device-side number of hits                                                     */
+    uint32_t n_max;            /* upper bound used for the grid                                                  */
+    float *bursts_out;         /* the extraction launches: [n_max][AM_BURST], or null (am_launch_slice: unused)   */
+    am_tag *tags_out;          /* likewise                                                                       */
+    const uint32_t *crc_pow;
+    am_packet *packets;
+    const uint32_t *scalars;   /* the context's device block (AM_SW_*)                                           */
+    uint32_t *host_out;        /* the context's pinned block (AM_PW_*), or null                                  */
+    const uint32_t *Mp;        /* or null: the scan's device-side candidate count, for host_out[AM_PW_CANDIDATES] */
+    int fix_bits;
+    int gate;
+};
+/* the time tags of the extraction launches: tt[0..ntt) device array in ascending offset order */
+struct am_stamp {
+    uint64_t base_abs;         /* absolute index of array coordinate 0                                           */
+    uint64_t rate;
+    const am_time_tag *tt;
+    uint32_t ntt;
+};
+/* extraction + slicing of the emitted preambles in one launch, from dense bb.  chip_idx: device table of the 240 soft chips' sample
+ * offsets int(j * samples per chip) (null: j * spc); hist0: history items of the preamble block (the tag's item count = stream
+ * index + hist0) */
+struct am_dense_src {
+    const float *bb;
+    const int *chip_idx;
+    int hist0;
+    long long e_off;
+};
+/* (emit_idx: one 16-byte record per hit, as am_emit_args describes) */
+hipError_t am_launch_extract_slice(const am_records &r, const am_dense_src &src, int spc, const uint4 *emit_idx, const am_stamp &st,
+                                   const am_slice_out &o, hipStream_t s);
 /* the same when bb exists only around the candidates: the burst is recomputed from IQ (iq[0] = absolute sample src_abs0) */
-hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long long src_abs1, int use_pmf, float s1,
-                                      const float *inavg, int spc, const uint4 *emit_idx, const uint32_t *n_ptr,
-                                      uint32_t n_max, const uint32_t *pos, const uint32_t *e, uint64_t base_abs,
-                                      uint64_t rate, const am_time_tag *tt, uint32_t ntt, float *bursts_out,
-                                      am_tag *tags_out, const uint32_t *crc_pow, am_packet *packets,
-                                      const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                      const uint32_t *Mp, int fix_bits, int gate);
+struct am_iq_src {
+    const float *iq;
+    long long src_abs0, src_abs1;
+    int use_pmf;
+    float s1;
+    int spc;
+};
+hipError_t am_launch_extract_slice_iq(const am_records &r, const am_iq_src &src, const uint4 *emit_idx, const am_stamp &st,
+                                      const am_slice_out &o, hipStream_t s);
+/* slicing alone, of bursts and tags that exist */
+hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const am_slice_out &o, hipStream_t s);
+
 /* ---- address gate (am_set_address_gate; am_gate.inc) ----------------------------------------------------
  * One record per hit index, written by lane 0 of the slicing wave (am_slice_wave<FIX, 1>) into DEVICE memory: the packet
  * array is pinned host memory, which a kernel does not read back. */
@@ -305,7 +432,6 @@ struct am_gate_rec {
 #define AM_GC_TEACH 1u   /* DF11 / DF17, syndrome 0 as sliced: teaches its address, kept                                       */
 #define AM_GC_TEST 2u    /* DF0/4/5/16/20/21: kept iff the address was taught at most ttl item counts before                   */
 #define AM_GC_OTHER 3u   /* any other format: mode 1 keeps it, mode 2 drops it                                                 */
-#define AM_GATE_REC_WORD 14   /* scalars[14..15] of the context's device block: the address of the record array               */
 #define AM_GATE_MAP_SLOTS (1u << 18)   /* the context's map; three quarters may be taken: 196 608 addresses alive               */
 struct am_gate_args {
     const am_gate_rec *rec;
@@ -334,19 +460,8 @@ void am_gate_scratch_layout(am_gate_args &a, void *scratch, uint32_t slots);
 hipError_t am_launch_gate(const am_gate_args &a, uint32_t n_max, hipStream_t s);   /* zero the call's table, teach, test     */
                                                                                    /* (a.rl: and repair)                      */
 hipError_t am_launch_gate_commit(const am_gate_args &a, hipStream_t s);            /* a.n records of an ACCEPTED scan         */
-/* cnt_dst[0..2] = taught, passed, dropped; rl (a.rl, or null): cnt_dst[5..6] = repaired, ambiguous */
-hipError_t am_launch_gate_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl,
-                                 uint32_t *cnt_dst, hipStream_t s);
-
-/* packets[i].reserved[0] = 1 when the reference would post the message, else 0.
- * fix_bits (all three launches; no default: a caller that forgot it would run without the repair and nobody would notice):
- * which instantiation am_k_*<FIX> runs -- 0 = the kernels as they are without the repair; 1, 2 = DF11 / DF17 replies with up to
- * that many wrong bits are repaired (am_set_fix_errors) and the number flipped is left in reserved[1].
- * gate (likewise): 1 = am_k_*<FIX, 1>, which also leaves an am_gate_rec per hit at the address in scalars[AM_GATE_REC_WORD]
- * (scalars must not be null then); 2 = am_k_*<FIX, 2>: the same, and an address/parity record carries its DF (am_k_gate_repair);
- * 0 = the kernels as they are without the gate */
-hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const uint32_t *n_ptr, uint32_t n_max,
-                           const uint32_t *crc_pow, am_packet *packets, const uint32_t *scalars,
-                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits, int gate);
+/* the completion ticket of a gated scan.  pin: the context's pinned block -- pin[AM_PW_TICKET] = seq, pin[AM_PW_GATE_TAUGHT ..
+ * AM_PW_GATE_DROPPED] = taught, passed, dropped; rl (a.rl, or null): pin[AM_PW_REPAIRED], pin[AM_PW_AMBIGUOUS] */
+hipError_t am_launch_gate_ticket(uint32_t *pin, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl, hipStream_t s);
 
 #endif

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "am_internal.h"
+#include "am_dispatch.h"
 #include "am_fe_stream.h"
 
 // keeps a loaded value where it is in the program (the compiler otherwise sinks loads to their first use, behind branches)
@@ -409,14 +410,12 @@ am_k_refine(const float *__restrict__ bb, const float *__restrict__ avg, am_geom
     tgt[g] = ok ? (e + (uint32_t)G.B) : (e + 1u);   // :237 / :209
 }
 
-hipError_t am_launch_refine(const float *bb, const float *avg, const am_geom &g, float thr_lin,
-                            const uint32_t *cand_seg, uint32_t seg_stride, const uint32_t *blk_off,
-                            uint32_t nblk, uint32_t M, uint32_t *pos, uint32_t *e, uint32_t *tgt,
-                            float *inavg, uint8_t *valid, hipStream_t s)
+hipError_t am_launch_refine(const am_refine_in &in, const am_geom &g, const uint32_t *cand_seg, uint32_t seg_stride,
+                            const uint32_t *blk_off, uint32_t nblk, const am_records &r, hipStream_t s)
 {
-    if (M == 0) return hipSuccess;
-    hipLaunchKernelGGL(am_k_refine, dim3((M + 255) / 256), dim3(256), 0, s, bb, avg, g, thr_lin, cand_seg,
-                       seg_stride, blk_off, nblk, M, pos, e, tgt, inavg, valid);
+    if (r.M == 0) return hipSuccess;
+    hipLaunchKernelGGL(am_k_refine, dim3((r.M + 255) / 256), dim3(256), 0, s, in.bb, in.avg, g, in.thr_lin, cand_seg,
+                       seg_stride, blk_off, nblk, r.M, r.pos, r.e, r.tgt, r.inavg, r.valid);
     return hipGetLastError();
 }
 
@@ -1187,17 +1186,15 @@ am_k_refine_late(const float *__restrict__ bb, const float *__restrict__ avg_spa
     if (g == M - 1u) jump0[M] = M;
 }
 
-hipError_t am_launch_refine_late(const float *bb, const float *avg_sparse, const uint32_t *pos, uint32_t M, int spc,
-                                 float thr_lin, uint32_t end_j, uint32_t *e, uint32_t *tgt, float *inavg, uint8_t *valid,
-                                 uint32_t *jump0, hipStream_t s, const uint32_t *Mp, const float *vmax, const am_fe_layout &l,
-                                 const float *bb_max)
+hipError_t am_launch_refine_late(const am_refine_in &in, int spc, const am_records &r, const float *vmax, const am_fe_layout &l,
+                                 const float *bb_max, hipStream_t s)
 {
     const uint32_t vspan = l.vspan(), nv = l.nv();
-    if (M == 0) return hipSuccess;
-    if (spc > 32 || spc < 1 || !vmax || vspan == 0 || nv == 0 || !jump0) return hipErrorInvalidValue;   // (the rounding bound is stated for 4 spc <= 128 terms)
-    if (bb_max && (spc != 32 || (reinterpret_cast<uintptr_t>(bb) & 15u) != 0)) return hipErrorInvalidValue;   // (rows of 32 samples, 16-byte aligned)
-    hipLaunchKernelGGL(am_k_refine_late, dim3((M + AM_RCB - 1) / AM_RCB), dim3(AM_RCB), 0, s, bb, avg_sparse, pos, M, spc, thr_lin,
-                       end_j, e, tgt, inavg, valid, jump0, Mp, vmax, vspan, nv, bb_max);
+    if (r.M == 0) return hipSuccess;
+    if (spc > 32 || spc < 1 || !vmax || vspan == 0 || nv == 0 || !r.jump0) return hipErrorInvalidValue;   // (the rounding bound is stated for 4 spc <= 128 terms)
+    if (bb_max && (spc != 32 || (reinterpret_cast<uintptr_t>(in.bb) & 15u) != 0)) return hipErrorInvalidValue;   // (rows of 32 samples, 16-byte aligned)
+    hipLaunchKernelGGL(am_k_refine_late, dim3((r.M + AM_RCB - 1) / AM_RCB), dim3(AM_RCB), 0, s, in.bb, in.avg, r.pos, r.M, spc,
+                       in.thr_lin, in.end_j, r.e, r.tgt, r.inavg, r.valid, r.jump0, r.Mp, vmax, vspan, nv, bb_max);
     return hipGetLastError();
 }
 
@@ -1257,7 +1254,7 @@ am_k_cblk_exit(const uint32_t *__restrict__ jump0, uint32_t Mcap, uint32_t headw
     const uint32_t M = am_count(Mcap, Mp);
     // resume position and hit flag start from zero a launch AHEAD of the one that raises them: inside am_k_cblk_visit the
     // walker's cur0 and the markers' targets are atomics from different XCDs, and a plain store among them is not ordered
-    if (scalars && blockIdx.x == 0 && threadIdx.x == 0) { scalars[0] = 0u; scalars[1] = 0u; }
+    if (scalars && blockIdx.x == 0 && threadIdx.x == 0) { scalars[AM_SW_RESUME] = 0u; scalars[AM_SW_HIT] = 0u; }
     const uint32_t base = blockIdx.x * AM_CB;
     if (base >= M) {                                          // (capacity launch: nothing here)
         for (uint32_t i = threadIdx.x; i < headw; i += blockDim.x) headlink[(size_t)blockIdx.x * headw + i] = (uint16_t)AM_CB_END;
@@ -1324,8 +1321,8 @@ am_k_cblk_exit(const uint32_t *__restrict__ jump0, uint32_t Mcap, uint32_t headw
 }
 
 // entry[b] = node at which the scan that starts at position cur0 enters block b, AM_CB_NONE if it
-// jumps over the block.  scalars[0] = cur0 (the emit kernel raises it to the resume position),
-// scalars[1] = 0.
+// jumps over the block.  scalars[AM_SW_RESUME] = cur0 (the emit kernel raises it to the resume position),
+// scalars[AM_SW_HIT] = 0.
 // The walk itself is sequential (one hop per block), so its inner loop is made as short as it can
 // be: the head table is turned into "next table slot" links (16 bit: slot = block * headw + index),
 // and a hop is one dependent LDS read plus one LDS write that records the block's entry; node
@@ -1436,8 +1433,8 @@ __device__ __forceinline__ uint64_t am_shard_entry_wave(const am_shard_exit *__r
 }
 
 // entry[b] = node at which the scan that starts at position cur0 enters block b, AM_CB_NONE if it
-// jumps over the block.  scalars[0] = cur0 (the emit kernel raises it to the resume position),
-// scalars[1] = 0.
+// jumps over the block.  scalars[AM_SW_RESUME] = cur0 (the emit kernel raises it to the resume position),
+// scalars[AM_SW_HIT] = 0.
 // The walk is one hop per block (a dependent LDS read each), so it is done on two levels: the blocks are cut into
 // groups of AM_CB_GROUP; (1) in parallel, from EVERY head slot of every group's first block, the slot at which the
 // orbit leaves the group (<= AM_CB_GROUP hops each); (2) one lane goes from group to group through that table;
@@ -1447,7 +1444,7 @@ __device__ __forceinline__ uint64_t am_shard_entry_wave(const am_shard_exit *__r
 // The body of the walk, for am_k_cblk_walk and for the walker of am_k_cblk_visit (FUSED).  All 1024 threads call it; lnk = dynamic
 // LDS (am_chain_walk_lds_bytes), *cur0_sh = the scan's start position (written before the call, read behind the first barrier).
 // FUSED: every block's entry also goes out as one {epoch, entry} word (entw[]: the payload-in-word pattern of am_chain_prefix,
-// relaxed device-scope stores, never reset), and scalars[0] is RAISED to cur0 with the markers' own atomic (am_k_cblk_exit
+// relaxed device-scope stores, never reset), and scalars[AM_SW_RESUME] is RAISED to cur0 with the markers' own atomic (am_k_cblk_exit
 // cleared it a launch ahead).
 template <bool FUSED>
 __device__ __forceinline__ void am_cblk_walk_body(uint16_t *lnk, uint32_t *seg_sh, uint32_t *root_sh, const uint32_t *cur0_sh,
@@ -1483,8 +1480,8 @@ __device__ __forceinline__ void am_cblk_walk_body(uint16_t *lnk, uint32_t *seg_s
     __syncthreads();
     const uint32_t cur0 = *cur0_sh;
     if (threadIdx.x == 0) {
-        if (FUSED) { if (cur0) atomicMax(&scalars[0], cur0); }
-        else { scalars[0] = cur0; scalars[1] = 0u; }
+        if (FUSED) { if (cur0) atomicMax(&scalars[AM_SW_RESUME], cur0); }
+        else { scalars[AM_SW_RESUME] = cur0; scalars[AM_SW_HIT] = 0u; }
     }
     if (stride && lo < M && p_hi >= cur0 && (lo == 0 || p_lo < cur0)) seg = lo;
     __syncthreads();
@@ -1705,25 +1702,7 @@ am_k_cblk_exit_table(const uint32_t *__restrict__ pos, const uint32_t *__restric
     }
 }
 
-// What the scan does with the candidates it visits (preamble_impl.cc:209-237).
-struct am_emit_args {
-    const uint8_t *valid;
-    const uint32_t *pos, *e, *tgt;
-    const float *inavg;             // reference level of every candidate (goes into the hit records)
-    uint32_t emit_max;              // room rule (:212): a valid hit too close to the end of the stream is not
-                                    // emitted (and nothing after it can be)
-    uint32_t own_lo, own_hi;        // first-stage positions this GPU's time chunk owns (everything on one GPU)
-    uint4 *emit_idx;                // out: the candidates to extract, in position order: {candidate index, first-stage position,
-                                    // refined position, reference level (bits)} -- everything the extraction kernels need of a hit
-                                    // in ONE load (round 5: index -> e / inavg / pos was a dependent memory round trip per hit)
-    uint32_t *n_out;                // out: how many
-    unsigned long long *slots;      // chained scan of the per-block hit counts (am_chain_prefix)
-    uint32_t epoch;
-    uint32_t *ticket;               // ... and the counter its places are drawn from (am_chain_place)
-    uint32_t ticket_base;
-    uint32_t *scalars;              // [0]: raised to the largest resume target of a visited candidate
-    int want_resume;
-};
+// (am_emit_args, what the scan does with the candidates it visits: am_internal.h)
 
 // The marking of one block, for am_k_cblk_mark (NT = 256 threads, the block's entry known when it starts) and for the markers
 // of am_k_cblk_visit (FUSED: NT = 1024, the entry arrives from the walker of the SAME launch).  NT / 64 waves, AM_CB / NT nodes
@@ -1733,7 +1712,7 @@ struct am_emit_args {
 // (am_cblk_walk_body<true> stores it: relaxed device-scope, the word carries its payload, so no fence on either side) and
 // hands the value round through LDS.  The walker holds place 0 of the launch's tickets, so it is running whenever somebody
 // polls; should its word never come (AM_CHAIN_SPIN_MAX polls, ~2 s), the block goes on WITHOUT an entry -- no hits, no
-// stores -- and raises scalars[9]: AM_EHIP at the C ABI, as when am_chain_prefix gives up.
+// stores -- and raises scalars[AM_SW_CHAIN_ERR]: AM_EHIP at the C ABI, as when am_chain_prefix gives up.
 template <int NT, bool FUSED>
 __device__ __forceinline__ void am_cblk_mark_body(const uint32_t *__restrict__ jump0, const uint32_t *__restrict__ entry,
                                                   const unsigned long long *entw, uint32_t M, uint32_t blk, uint32_t nblk,
@@ -1824,7 +1803,7 @@ __device__ __forceinline__ void am_cblk_mark_body(const uint32_t *__restrict__ j
                     __builtin_amdgcn_s_sleep(1);
                     v = __hip_atomic_load(&entw[blk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                if (failed) ea.scalars[9] = 1u;
+                if (failed) ea.scalars[AM_SW_CHAIN_ERR] = 1u;
                 *ent_sh = failed ? AM_CB_NONE : (uint32_t)v;
             }
             __syncthreads();
@@ -1897,13 +1876,13 @@ __device__ __forceinline__ void am_cblk_mark_body(const uint32_t *__restrict__ j
     if (threadIdx.x == 0 && ea.want_resume) {
         uint32_t m = 0;
         for (int k = 0; k < NW; ++k) m = wmax[k] > m ? wmax[k] : m;
-        if (m) atomicMax(&ea.scalars[0], m);
+        if (m) atomicMax(&ea.scalars[AM_SW_RESUME], m);
     }
     AM_MSTAMP();
     const uint32_t before = am_chain_prefix(ea.slots, blk, ea.epoch, tot, red);
     AM_MSTAMP();                                              // chain prefix
     if (before == AM_CHAIN_FAIL) {                            // (uniform) a place was never published: no stores, the error word, no hits
-        if (threadIdx.x == 0) { ea.scalars[9] = 1u; if (blk == nblk - 1) *ea.n_out = 0u; }
+        if (threadIdx.x == 0) { ea.scalars[AM_SW_CHAIN_ERR] = 1u; if (blk == nblk - 1) *ea.n_out = 0u; }
         return;
     }
     uint32_t off = before;
@@ -2044,56 +2023,50 @@ static hipError_t am_chain_walk_lds(const void *kernel, std::atomic<bool> (&done
 }
 
 // step 1 (independent of where the scan starts): successor array + per-block exits
-hipError_t am_launch_chain_prepare(const uint32_t *pos, const uint32_t *tgt, uint32_t M, uint32_t *jump0,
-                                   uint32_t *scratch, int want_last, hipStream_t s, const uint32_t *Mp, int have_succ,
-                                   uint32_t *scalars)
+hipError_t am_launch_chain_prepare(const am_records &r, uint32_t *scratch, int want_last, int have_succ, uint32_t *scalars,
+                                   hipStream_t s)
 {
-    if (M == 0) return hipSuccess;
-    const am_chain_layout L = am_chain_layout_of(M);
-    if (!have_succ)                                           // (am_k_cand already wrote the successors)
-    hipLaunchKernelGGL(am_k_chain_succ, dim3(am_grid((uint64_t)M + 1, 256)), dim3(256), 0, s, pos, tgt, M, jump0, Mp);
-    hipLaunchKernelGGL(am_k_cblk_exit, dim3(L.nblk), dim3(AM_CB_THREADS), 0, s, jump0, M, L.headw, scratch,
-                       want_last ? scratch + L.off_last : nullptr, reinterpret_cast<uint16_t *>(scratch + L.off_head), Mp, scalars);
+    if (r.M == 0) return hipSuccess;
+    const am_chain_layout L = am_chain_layout_of(r.M);
+    if (!have_succ)                                           // (the refinement already wrote the successors)
+        hipLaunchKernelGGL(am_k_chain_succ, dim3(am_grid((uint64_t)r.M + 1, 256)), dim3(256), 0, s, r.pos, r.tgt, r.M, r.jump0, r.Mp);
+    hipLaunchKernelGGL(am_k_cblk_exit, dim3(L.nblk), dim3(AM_CB_THREADS), 0, s, r.jump0, r.M, L.headw, scratch,
+                       want_last ? scratch + L.off_last : nullptr, reinterpret_cast<uint16_t *>(scratch + L.off_head), r.Mp, scalars);
     return hipGetLastError();
 }
 
-// steps 2 + 3: which candidates the scan that starts at position cur0 visits, and what it does with them:
-// emit_idx[0 .. *n_out) = the hits in position order, scalars[0] = resume position.
+// steps 2 + 3: which candidates the scan that starts at position w.cur0 visits, and what it does with them:
+// ea.emit_idx[0 .. *ea.n_out) = the hits in position order, ea.scalars[AM_SW_RESUME] = resume position.
 // Two forms.  FUSED (am_k_cblk_visit, one launch): for a plain scan -- the start position comes from the host, nobody waits for
-// the walk alone, am_launch_chain_prepare cleared scalars[0 .. 1], the host waits for this scan before it enqueues another
-// (entry_slots != null says all that: one {epoch, entry} word per block, zero at allocation) -- whose nblk + 1 workgroups of 1024 threads are resident in one round (one per CU).  SEPARATE
-// (am_k_cblk_walk, then am_k_cblk_mark): everything else.  walk_mode (test builds): AM_WALK_SEPARATE / AM_WALK_FUSED force
-// either form where both are legal, the CU count notwithstanding.  *fused_out: which one ran.
-hipError_t am_launch_chain_visit(const uint32_t *pos, const uint32_t *jump0, uint32_t M, uint32_t cur0,
-                                 uint32_t *scratch, const uint8_t *valid, const uint32_t *e, const uint32_t *tgt,
-                                 uint32_t emit_max, uint32_t own_lo, uint32_t own_hi, uint4 *emit_idx, uint32_t *n_out,
-                                 unsigned long long *slots, uint32_t epoch, uint32_t *ticket, uint32_t *ticket_base,
-                                 uint32_t *scalars, int want_resume, hipStream_t s, const uint32_t *Mp, const am_entry_src *entry_src,
-                                 const float *inavg, hipEvent_t after_walk, unsigned long long *entry_slots, int walk_mode,
-                                 int *fused_out)
+// the walk alone, am_launch_chain_prepare cleared scalars[AM_SW_RESUME] and [AM_SW_HIT], the host waits for this scan before it
+// enqueues another (w.entry_slots != null says all that: one {epoch, entry} word per block, zero at allocation) -- whose nblk + 1
+// workgroups of 1024 threads are resident in one round (one per CU).  SEPARATE (am_k_cblk_walk, then am_k_cblk_mark): everything
+// else.  w.walk_mode (test builds): AM_WALK_SEPARATE / AM_WALK_FUSED force either form where both are legal, the CU count
+// notwithstanding.  *fused_out: which one ran.
+hipError_t am_launch_chain_visit(const am_records &r, const am_emit_args &ea_in, const am_walk_req &w, uint32_t *ticket_base,
+                                 int *fused_out, hipStream_t s)
 {
     if (fused_out) *fused_out = 0;
-    if (M == 0) return hipSuccess;
-    const am_chain_layout L = am_chain_layout_of(M);
+    if (r.M == 0) return hipSuccess;
+    const am_chain_layout L = am_chain_layout_of(r.M);
     const size_t lds = am_chain_walk_lds_bytes(L.nblk, L.headw);
     if (lds > AM_CB_WALK_LDS) return hipErrorInvalidValue;   // (more than ~75 000 blocks of 2048 candidates in one scan)
-    am_emit_args ea;
-    ea.valid = valid; ea.pos = pos; ea.e = e; ea.tgt = tgt; ea.inavg = inavg; ea.emit_max = emit_max; ea.own_lo = own_lo;
-    ea.own_hi = own_hi; ea.emit_idx = emit_idx; ea.n_out = n_out; ea.slots = slots; ea.epoch = epoch; ea.scalars = scalars;
-    ea.want_resume = want_resume;
-    ea.ticket = ticket; ea.ticket_base = *ticket_base;
-    bool fused = entry_slots && !entry_src && !after_walk && walk_mode != AM_WALK_SEPARATE;
+    am_emit_args ea = ea_in;
+    ea.valid = r.valid; ea.pos = r.pos; ea.e = r.e; ea.tgt = r.tgt; ea.inavg = r.inavg;
+    ea.ticket_base = *ticket_base;
+    uint32_t *const scratch = w.scratch;
+    bool fused = w.entry_slots && !w.entry_src && !w.after_walk && w.walk_mode != AM_WALK_SEPARATE;
 #if !defined(AM_HIP_EMULATION)                                // (the emulation runs one workgroup after the other: nothing to be resident)
-    if (fused && walk_mode != AM_WALK_FUSED) fused = L.nblk + 1u <= (uint32_t)am_device_cus();
+    if (fused && w.walk_mode != AM_WALK_FUSED) fused = L.nblk + 1u <= (uint32_t)am_device_cus();
 #endif
     if (fused) {
         static std::atomic<bool> attr_set[64];
         if (hipError_t rc = am_chain_walk_lds(reinterpret_cast<const void *>(&am_k_cblk_visit), attr_set); rc != hipSuccess)
             return rc;
         const size_t vlds = ((lds > AM_CB_MARK_LDS ? lds : AM_CB_MARK_LDS) + 15) & ~(size_t)15;
-        hipLaunchKernelGGL(am_k_cblk_visit, dim3(L.nblk + 1u), dim3(AM_CB_VTHREADS), vlds, s, pos, scratch,
-                           reinterpret_cast<const uint16_t *>(scratch + L.off_head), jump0, M, L.nblk, L.headw, cur0,
-                           scratch + L.off_entry, entry_slots, ea, Mp);
+        hipLaunchKernelGGL(am_k_cblk_visit, dim3(L.nblk + 1u), dim3(AM_CB_VTHREADS), vlds, s, r.pos, scratch,
+                           reinterpret_cast<const uint16_t *>(scratch + L.off_head), r.jump0, r.M, L.nblk, L.headw, w.cur0,
+                           scratch + L.off_entry, w.entry_slots, ea, r.Mp);
         const hipError_t rc = hipGetLastError();
         if (rc == hipSuccess) { *ticket_base += L.nblk + 1u; if (fused_out) *fused_out = 1; }   // (every workgroup of a launch that happened draws one)
         return rc;
@@ -2101,26 +2074,23 @@ hipError_t am_launch_chain_visit(const uint32_t *pos, const uint32_t *jump0, uin
     static std::atomic<bool> attr_set[64];
     if (hipError_t rc = am_chain_walk_lds(reinterpret_cast<const void *>(&am_k_cblk_walk), attr_set); rc != hipSuccess)
         return rc;
-    am_entry_src es;
-    if (entry_src) es = *entry_src;
-    else { es.msgs = nullptr; es.world = 0; es.rank = 0; es.cap = 0; es.base_abs = 0; es.flags = nullptr; es.exit_out = nullptr; es.cur_in = nullptr; }
-    hipLaunchKernelGGL(am_k_cblk_walk, dim3(1), dim3(1024), lds, s, pos, scratch, reinterpret_cast<const uint16_t *>(scratch + L.off_head), M, L.nblk,
-                       L.headw, cur0, scratch + L.off_entry, scalars, Mp, es);
+    const am_entry_src es = w.entry_src ? *w.entry_src : am_entry_src{};   // (msgs == null: the start position is w.cur0)
+    hipLaunchKernelGGL(am_k_cblk_walk, dim3(1), dim3(1024), lds, s, r.pos, scratch, reinterpret_cast<const uint16_t *>(scratch + L.off_head),
+                       r.M, L.nblk, L.headw, w.cur0, scratch + L.off_entry, ea.scalars, r.Mp, es);
     if (hipError_t rc = hipGetLastError(); rc != hipSuccess) return rc;   // (the walk's launch)
     // (am_spipe: the walk has written where the scan leaves this chunk -- all the next chunk's resolve step waits for)
-    if (after_walk) if (hipError_t rc = hipEventRecord(after_walk, s); rc != hipSuccess) return rc;
-    hipLaunchKernelGGL(am_k_cblk_mark, dim3(L.nblk), dim3(AM_CB_THREADS), 0, s, jump0, scratch + L.off_entry, M, ea,
-                       Mp);
+    if (w.after_walk) if (hipError_t rc = hipEventRecord(w.after_walk, s); rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(am_k_cblk_mark, dim3(L.nblk), dim3(AM_CB_THREADS), 0, s, r.jump0, scratch + L.off_entry, r.M, ea, r.Mp);
     const hipError_t rc = hipGetLastError();
     if (rc == hipSuccess) *ticket_base += L.nblk;            // (every workgroup of a launch that happened draws one)
     return rc;
 }
 
 // exit table of a time chunk for its first n candidates (needs am_launch_chain_prepare(want_last = 1))
-hipError_t am_launch_chain_exit_table(const uint32_t *pos, const uint32_t *tgt, uint32_t M, uint32_t n,
-                                      uint32_t lead_end, uint32_t *scratch, uint64_t base_abs, am_shard_exit *table,
-                                      hipStream_t s, const uint32_t *Mp, am_shard_exit *header, const uint64_t *carry)
+hipError_t am_launch_chain_exit_table(const am_records &r, uint32_t n, uint32_t lead_end, uint32_t *scratch, uint64_t base_abs,
+                                      const am_exit_dst &dst, hipStream_t s)
 {
+    const uint32_t M = r.M;
     if (n == 0 || M == 0) return hipSuccess;
     const am_chain_layout L = am_chain_layout_of(M);
     static std::atomic<bool> attr_set[64];
@@ -2129,8 +2099,9 @@ hipError_t am_launch_chain_exit_table(const uint32_t *pos, const uint32_t *tgt, 
         return rc;
     const size_t lds = am_chain_walk_lds_bytes(L.nblk, L.headw);          // (links + group exits: the walk's layout holds both)
     if (lds > AM_CB_WALK_LDS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(am_k_cblk_exit_table, dim3(1), dim3(1024), lds, s, pos, tgt, scratch, scratch + L.off_last,
-                       reinterpret_cast<const uint16_t *>(scratch + L.off_head), M, L.nblk, L.headw, n, lead_end, base_abs, table, Mp, header, carry);
+    hipLaunchKernelGGL(am_k_cblk_exit_table, dim3(1), dim3(1024), lds, s, r.pos, r.tgt, scratch, scratch + L.off_last,
+                       reinterpret_cast<const uint16_t *>(scratch + L.off_head), M, L.nblk, L.headw, n, lead_end, base_abs, dst.table, r.Mp,
+                       dst.header, dst.carry);
     return hipGetLastError();
 }
 
@@ -2160,12 +2131,10 @@ am_k_shard_entry(const am_shard_exit *__restrict__ msgs, uint32_t world, uint32_
     if (!bad) *exit_out = leave;
 }
 
-hipError_t am_launch_shard_entry(const am_shard_exit *msgs, uint32_t world, uint32_t rank, uint32_t cap, uint64_t base_abs,
-                                 uint32_t *cur0_out, uint32_t *flags, uint64_t *exit_out, hipStream_t s, const uint64_t *cur_in,
-                                 uint64_t *carry_out)
+hipError_t am_launch_shard_entry(const am_entry_src &es, uint32_t *cur0_out, hipStream_t s)
 {
-    hipLaunchKernelGGL(am_k_shard_entry, dim3(1), dim3(AM_WAVE), 0, s, msgs, world, rank, cap, base_abs, cur0_out, flags, exit_out,
-                       (am_shard_exit *)nullptr, (const uint64_t *)nullptr, cur_in, carry_out);
+    hipLaunchKernelGGL(am_k_shard_entry, dim3(1), dim3(AM_WAVE), 0, s, es.msgs, es.world, es.rank, es.cap, es.base_abs, cur0_out,
+                       es.flags, es.exit_out, (am_shard_exit *)nullptr, (const uint64_t *)nullptr, es.cur_in, es.carry_out);
     return hipGetLastError();
 }
 hipError_t am_launch_shard_header(am_shard_exit *header, const uint64_t *carry, hipStream_t s)
@@ -2298,7 +2267,7 @@ __device__ __forceinline__ int am_fix_errors(unsigned long long &m0, unsigned lo
 // one wave slices burst b (240 soft chips, global memory or LDS); lane 0 files the packet under index i.
 // FIX: wrong bits to repair (am_fix_errors above): 1 or 2; 0 is the code as it was before the repair existed.
 // GATE: 1 = lane 0 also files the hit's part in the address gate (am_gate.inc) as record i of the array whose address the
-// context keeps in scalars[AM_GATE_REC_WORD] (device memory; a kernel argument of its own would change the <FIX, 0> kernels'
+// context keeps in scalars[AM_SW_GATE_REC] (device memory; a kernel argument of its own would change the <FIX, 0> kernels'
 // descriptors); 0 is the code as it was before the gate existed, and never looks at scalars.  2 (am_set_address_repair) = 1, and
 // the record of an address/parity reply carries its DF above the 24 bits of the syndrome.
 template <int FIX, int GATE>
@@ -2378,7 +2347,7 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
                     r.cls = AM_GC_OTHER;
                 }
             }
-            am_gate_rec *grec = *reinterpret_cast<am_gate_rec *const *>(scalars + AM_GATE_REC_WORD);
+            am_gate_rec *grec = *reinterpret_cast<am_gate_rec *const *>(scalars + AM_SW_GATE_REC);
             grec[i] = r;
         }
         if (!ok) {
@@ -2409,9 +2378,9 @@ am_k_slice(const float *__restrict__ bursts, const am_tag *__restrict__ tags, co
     const uint32_t i = blockIdx.x * (blockDim.x / AM_WAVE) + threadIdx.x / AM_WAVE;
     // hit count and scan resume position go straight to pinned host memory (no extra copies)
     if (host_out && blockIdx.x == 0 && threadIdx.x == 0) {
-        host_out[0] = *n_ptr;
-        host_out[1] = scalars[0];
-        host_out[2] = Mp ? *Mp : 0u;                          // actual candidate count (speculative launches)
+        host_out[AM_PW_HITS] = *n_ptr;
+        host_out[AM_PW_RESUME] = scalars[AM_SW_RESUME];
+        host_out[AM_PW_CANDIDATES] = Mp ? *Mp : 0u;                          // actual candidate count (speculative launches)
     }
     if (i >= *n_ptr) return;                              // wave-uniform; device-side burst count
     const am_tag t = tags[i];                             // (lane 0 uses it)
@@ -2437,10 +2406,10 @@ am_k_extract_slice(const float *__restrict__ bb, const float *__restrict__ inavg
     const int lane = threadIdx.x & (AM_WAVE - 1), wv = threadIdx.x / AM_WAVE;
     const uint32_t i = blockIdx.x * (blockDim.x / AM_WAVE) + wv;
     if (host_out && blockIdx.x == 0 && threadIdx.x == 0) {
-        host_out[0] = *n_ptr;
-        host_out[1] = scalars[0];
-        host_out[2] = Mp ? *Mp : 0u;                          // actual candidate count (speculative launches)
-        host_out[5] = scalars[9];                             // a chained scan of this step gave up (am_chain_prefix)
+        host_out[AM_PW_HITS] = *n_ptr;
+        host_out[AM_PW_RESUME] = scalars[AM_SW_RESUME];
+        host_out[AM_PW_CANDIDATES] = Mp ? *Mp : 0u;                          // actual candidate count (speculative launches)
+        host_out[AM_PW_CHAIN_ERR] = scalars[AM_SW_CHAIN_ERR];                            // a chained scan of this step gave up (am_chain_prefix)
     }
     if (i >= *n_ptr) return;                              // wave-uniform; device-side hit count
     const uint4 rec = emit_idx[i];                          // {candidate, first-stage position, refined position, reference level}
@@ -2461,26 +2430,15 @@ am_k_extract_slice(const float *__restrict__ bb, const float *__restrict__ inavg
     am_slice_wave<FIX, GATE>(sb[wv], t, i, lane, crc_pow, packets, scalars);
 }
 
-hipError_t am_launch_extract_slice(const float *bb, const float *inavg, int spc, const int *chip_idx, int hist0,
-                                   const uint4 *emit_idx,
-                                   const uint32_t *n_ptr, uint32_t n_max, const uint32_t *pos, const uint32_t *e,
-                                   uint64_t base_abs, long long e_off, uint64_t rate, const am_time_tag *tt,
-                                   uint32_t ntt, float *bursts_out, am_tag *tags_out, const uint32_t *crc_pow,
-                                   am_packet *packets, const uint32_t *scalars, uint32_t *host_out, hipStream_t s,
-                                   const uint32_t *Mp, int fix_bits, int gate)
+hipError_t am_launch_extract_slice(const am_records &r, const am_dense_src &src, int spc, const uint4 *emit_idx, const am_stamp &st,
+                                   const am_slice_out &o, hipStream_t s)
 {
-    if (n_max == 0) return hipSuccess;
-#define AM_XS_G(FIX, GATE)                                                                                                \
-    hipLaunchKernelGGL((am_k_extract_slice<FIX, GATE>), dim3(am_grid(n_max, 4)), dim3(256), 0, s, bb, inavg, spc, chip_idx, hist0,  \
-                       emit_idx, n_ptr, pos, e, base_abs, e_off, rate, tt, ntt, bursts_out, tags_out, crc_pow, packets,   \
-                       scalars, host_out, Mp)
-#define AM_XS(FIX)                                                                                                        \
-    do { if (gate == 2) AM_XS_G(FIX, 2); else if (gate) AM_XS_G(FIX, 1); else AM_XS_G(FIX, 0); } while (0)
-    if (fix_bits == 0) AM_XS(0);
-    else if (fix_bits == 1) AM_XS(1);
-    else AM_XS(2);
-#undef AM_XS
-#undef AM_XS_G
+    if (o.n_max == 0) return hipSuccess;
+    am_with_fix_gate(o.fix_bits, o.gate, [&](auto fix, auto gate) {
+        hipLaunchKernelGGL((am_k_extract_slice<decltype(fix)::value, decltype(gate)::value>), dim3(am_grid(o.n_max, 4)), dim3(256), 0, s,
+                           src.bb, r.inavg, spc, src.chip_idx, src.hist0, emit_idx, o.n_ptr, r.pos, r.e, st.base_abs, src.e_off, st.rate,
+                           st.tt, st.ntt, o.bursts_out, o.tags_out, o.crc_pow, o.packets, o.scalars, o.host_out, o.Mp);
+    });
     return hipGetLastError();
 }
 
@@ -2681,10 +2639,10 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
 #endif
     const uint32_t nhit = *n_ptr;                             // device-side hit count
     if (host_out && blockIdx.x == 0 && threadIdx.x == 0) {
-        host_out[0] = nhit;
-        host_out[1] = scalars[0];
-        host_out[2] = Mp ? *Mp : 0u;
-        host_out[5] = scalars[9];                             // a chained scan of this step gave up (am_chain_prefix)
+        host_out[AM_PW_HITS] = nhit;
+        host_out[AM_PW_RESUME] = scalars[AM_SW_RESUME];
+        host_out[AM_PW_CANDIDATES] = Mp ? *Mp : 0u;
+        host_out[AM_PW_CHAIN_ERR] = scalars[AM_SW_CHAIN_ERR];                            // a chained scan of this step gave up (am_chain_prefix)
     }
     const bool pmf = use_pmf != 0;
     const bool wide = (reinterpret_cast<uintptr_t>(iq) & 15u) == 0;
@@ -2763,63 +2721,36 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
 #endif
 }
 
-hipError_t am_launch_extract_slice_iq(const float *iq, long long src_abs0, long long src_abs1, int use_pmf, float s1,
-                                      const float *inavg, int spc, const uint4 *emit_idx, const uint32_t *n_ptr,
-                                      uint32_t n_max, const uint32_t *pos, const uint32_t *e, uint64_t base_abs,
-                                      uint64_t rate, const am_time_tag *tt, uint32_t ntt, float *bursts_out,
-                                      am_tag *tags_out, const uint32_t *crc_pow, am_packet *packets,
-                                      const uint32_t *scalars, uint32_t *host_out, hipStream_t s, const uint32_t *Mp,
-                                      int fix_bits, int gate)
+template <int SPC, int FIX, int GATE> struct am_xs_iq_key {};     // (names an instantiation's occupancy cache)
+
+hipError_t am_launch_extract_slice_iq(const am_records &r, const am_iq_src &src, const uint4 *emit_idx, const am_stamp &st,
+                                      const am_slice_out &o, hipStream_t s)
 {
-    if (n_max == 0) return hipSuccess;
-    // workgroups of 256 threads per CU: what the instantiation's registers allow (five at 32 samples per chip, where a lane
-    // holds a 34-sample window; eight at one or two samples per chip, where the kernel is a chain of memory round trips per
-    // hit and more hits in flight is all that helps), asked of the runtime once per device and instantiation
-    static std::atomic<int> per_cu[64][81];                  // (9 rates x repair of 0, 1, 2 bits x address gate off, on, on with its repair)
+    if (o.n_max == 0) return hipSuccess;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    auto resident_for = [&](const void *kernel, int slot) -> uint32_t {
-        int w = (dev >= 0 && dev < 64) ? per_cu[dev][slot].load(std::memory_order_acquire) : 0;
-        if (w <= 0) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, kernel, 256, 0) != hipSuccess || w <= 0) w = 5;
-            w = w > 8 ? 8 : w;
-            if (dev >= 0 && dev < 64) per_cu[dev][slot].store(w, std::memory_order_release);
-        }
-        return (uint32_t)w * (uint32_t)am_device_cus();
-    };
-#define AM_XS_IQ_G(S, SLOT, FIX, GATE)                                                                                    \
-    do {                                                                                                                  \
-        const uint32_t resident = resident_for(reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, FIX, GATE>), SLOT + 9 * FIX + 27 * GATE); \
-        const uint32_t grid = n_max < resident ? n_max : resident;                                                        \
-        hipLaunchKernelGGL((am_k_extract_slice_iq<S, FIX, GATE>), dim3(grid), dim3(256), 0, s, iq, src_abs0, src_abs1, use_pmf, s1, \
-                           inavg, emit_idx, n_ptr, pos, e, base_abs, rate, tt, ntt, bursts_out, tags_out, crc_pow,      \
-                           packets, scalars, host_out, Mp);                                                              \
-    } while (0)
-#define AM_XS_IQ_F(S, SLOT, FIX)                                                                                          \
-    do { if (gate == 2) AM_XS_IQ_G(S, SLOT, FIX, 2); else if (gate) AM_XS_IQ_G(S, SLOT, FIX, 1); else AM_XS_IQ_G(S, SLOT, FIX, 0); } while (0)
-#define AM_XS_IQ(S, SLOT)                                                                                                 \
-    do {                                                                                                                  \
-        if (fix_bits == 0) AM_XS_IQ_F(S, SLOT, 0);                                                                        \
-        else if (fix_bits == 1) AM_XS_IQ_F(S, SLOT, 1);                                                                   \
-        else AM_XS_IQ_F(S, SLOT, 2);                                                                                      \
-    } while (0)
-    if (spc == 1) use_pmf = 0;                               // (a one-sample window is the sample itself: s1 = 1)
-    switch (spc) {                                           // (the rates the streaming front ends serve)
-    case 32: AM_XS_IQ(32, 0); break;
-    case 20: AM_XS_IQ(20, 1); break;
-    case 16: AM_XS_IQ(16, 2); break;
-    case 10: AM_XS_IQ(10, 3); break;
-    case 8: AM_XS_IQ(8, 4); break;
-    case 4: AM_XS_IQ(4, 5); break;
-    case 5: AM_XS_IQ(5, 8); break;
-    case 2: AM_XS_IQ(2, 6); break;
-    case 1: AM_XS_IQ(1, 7); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef AM_XS_IQ
-#undef AM_XS_IQ_F
-#undef AM_XS_IQ_G
-    return hipGetLastError();
+    const int use_pmf = src.spc == 1 ? 0 : src.use_pmf;       // (a one-sample window is the sample itself: s1 = 1)
+    const bool known = am_with_spc(src.spc, [&](auto spc) {
+        am_with_fix_gate(o.fix_bits, o.gate, [&](auto fix, auto gate) {
+            constexpr int S = decltype(spc)::value, F = decltype(fix)::value, G = decltype(gate)::value;
+            // workgroups of 256 threads per CU: what the instantiation's registers allow (five at 32 samples per chip, where a
+            // lane holds a 34-sample window; eight at one or two samples per chip, where the kernel is a chain of memory round
+            // trips per hit and more hits in flight is all that helps), asked of the runtime once per device and instantiation
+            std::atomic<int> *cached = am_device_cache<am_xs_iq_key<S, F, G>>(dev);
+            int w = cached ? cached->load(std::memory_order_acquire) : 0;
+            if (w <= 0) {
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, F, G>), 256, 0) != hipSuccess || w <= 0) w = 5;
+                w = w > 8 ? 8 : w;
+                if (cached) cached->store(w, std::memory_order_release);
+            }
+            const uint32_t resident = (uint32_t)w * (uint32_t)am_device_cus();
+            const uint32_t grid = o.n_max < resident ? o.n_max : resident;
+            hipLaunchKernelGGL((am_k_extract_slice_iq<S, F, G>), dim3(grid), dim3(256), 0, s, src.iq, src.src_abs0, src.src_abs1, use_pmf,
+                               src.s1, r.inavg, emit_idx, o.n_ptr, r.pos, r.e, st.base_abs, st.rate, st.tt, st.ntt, o.bursts_out,
+                               o.tags_out, o.crc_pow, o.packets, o.scalars, o.host_out, o.Mp);
+        });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // Completion ticket: the last launch of a scan.  The host polls the pinned word instead of asking the
@@ -2845,21 +2776,13 @@ hipError_t am_launch_ticket(uint32_t *host_word, uint32_t seq, hipStream_t s, co
     return hipGetLastError();
 }
 
-hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const uint32_t *n_ptr, uint32_t n_max,
-                           const uint32_t *crc_pow, am_packet *packets, const uint32_t *scalars,
-                           uint32_t *host_out, hipStream_t s, const uint32_t *Mp, int fix_bits, int gate)
+hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const am_slice_out &o, hipStream_t s)
 {
-    if (n_max == 0) return hipSuccess;
-#define AM_SL_G(FIX, GATE)                                                                                                \
-    hipLaunchKernelGGL((am_k_slice<FIX, GATE>), dim3(am_grid(n_max, 4)), dim3(256), 0, s, bursts, tags, n_ptr, crc_pow, packets, scalars, \
-                       host_out, Mp)
-#define AM_SL(FIX)                                                                                                        \
-    do { if (gate == 2) AM_SL_G(FIX, 2); else if (gate) AM_SL_G(FIX, 1); else AM_SL_G(FIX, 0); } while (0)
-    if (fix_bits == 0) AM_SL(0);
-    else if (fix_bits == 1) AM_SL(1);
-    else AM_SL(2);
-#undef AM_SL
-#undef AM_SL_G
+    if (o.n_max == 0) return hipSuccess;
+    am_with_fix_gate(o.fix_bits, o.gate, [&](auto fix, auto gate) {
+        hipLaunchKernelGGL((am_k_slice<decltype(fix)::value, decltype(gate)::value>), dim3(am_grid(o.n_max, 4)), dim3(256), 0, s, bursts,
+                           tags, o.n_ptr, o.crc_pow, o.packets, o.scalars, o.host_out, o.Mp);
+    });
     return hipGetLastError();
 }
 

@@ -747,10 +747,8 @@ __global__ void __launch_bounds__(RS_NT, RS_WPS) am_k_refine_seg(am_rseg_args a)
 #endif
 }
 
-hipError_t am_launch_refine_seg(const uint32_t *bits, const uint32_t *wg_cnt, const float *wg_max, const am_fe_layout &l, uint32_t Mcap,
-                                const am_rows_args &rows, const float *avg_sparse, float thr_lin, uint32_t end_j, uint32_t *pos,
-                                uint32_t *e, uint32_t *tgt, float *inavg, uint8_t *valid, uint32_t *jump0, uint32_t *total_out,
-                                hipStream_t s)
+hipError_t am_launch_refine_seg(const am_fe_marks &m, const am_fe_layout &l, const am_rows_args &rows, const am_refine_in &in,
+                                const am_records &r, uint32_t *total_out, hipStream_t s)
 {
     const uint32_t nwg = l.nwg, words_per_wg = l.words_per_wg();
     if (nwg == 0 || l.nwords() == 0) return hipSuccess;
@@ -758,10 +756,10 @@ hipError_t am_launch_refine_seg(const uint32_t *bits, const uint32_t *wg_cnt, co
     if (l.wbits != 32 || l.lag != 288 || words_per_wg == 0 || !rows.iq || l.vspan() == 0 || l.nv() == 0) return hipErrorInvalidValue;
     if (!l.alike() && l.words_short() == 0) return hipErrorInvalidValue;   // (levelled: the short segments have a step too)
     am_rseg_args a;
-    a.bits = bits; a.wg_cnt = wg_cnt; a.wg_max = wg_max; a.nwg = nwg; a.words_per_wg = words_per_wg; a.nwords = l.nwords(); a.Mcap = Mcap;
-    a.vspan = l.vspan(); a.nv = l.nv(); a.end_j = end_j; a.iq = rows.iq; a.src_abs0 = rows.src_abs0; a.src_abs1 = rows.src_abs1;
-    a.out_abs0 = rows.out_abs0; a.avg_sparse = avg_sparse; a.s1 = rows.s1; a.thr_lin = thr_lin; a.pos = pos; a.e = e; a.tgt = tgt;
-    a.jump0 = jump0; a.total_out = total_out; a.inavg = inavg; a.valid = valid;
+    a.bits = m.bits; a.wg_cnt = m.wg_cnt; a.wg_max = m.wg_max; a.nwg = nwg; a.words_per_wg = words_per_wg; a.nwords = l.nwords(); a.Mcap = r.M;
+    a.vspan = l.vspan(); a.nv = l.nv(); a.end_j = in.end_j; a.iq = rows.iq; a.src_abs0 = rows.src_abs0; a.src_abs1 = rows.src_abs1;
+    a.out_abs0 = rows.out_abs0; a.avg_sparse = in.avg; a.s1 = rows.s1; a.thr_lin = in.thr_lin; a.pos = r.pos; a.e = r.e; a.tgt = r.tgt;
+    a.jump0 = r.jump0; a.total_out = total_out; a.inavg = r.inavg; a.valid = r.valid;
     // levelled segments: the first n_long of words_per_wg words, the others one step shorter
     a.n_long = l.alike() ? nwg : l.n_long;
     a.words_short = l.words_short();

@@ -264,13 +264,11 @@ hipError_t am_launch_energy(const float *bb, const uint32_t *pos, const uint32_t
                        energy, Mp);
     return hipGetLastError();
 }
-hipError_t am_launch_cand(const float *bb, const float *avg_sparse, const uint32_t *pos, const uint32_t *dcount,
-                          const uint32_t *off_local, const uint32_t *blk_base, const double *energy, uint32_t M,
-                          int spc, float thr_lin, uint32_t end_j, uint32_t *e, uint32_t *tgt, float *inavg,
-                          uint8_t *valid, uint32_t *jump0, hipStream_t s, const uint32_t *Mp)
+hipError_t am_launch_cand(const am_refine_in &in, const uint32_t *dcount, const uint32_t *off_local, const uint32_t *blk_base,
+                          const double *energy, int spc, const am_records &r, hipStream_t s)
 {
-    if (M == 0) return hipSuccess;
-    hipLaunchKernelGGL(am_k_cand, dim3((M + 255) / 256), dim3(256), 0, s, bb, avg_sparse, pos, dcount, off_local,
-                       blk_base, energy, M, spc, thr_lin, end_j, e, tgt, inavg, valid, jump0, Mp);
+    if (r.M == 0) return hipSuccess;
+    hipLaunchKernelGGL(am_k_cand, dim3((r.M + 255) / 256), dim3(256), 0, s, in.bb, in.avg, r.pos, dcount, off_local,
+                       blk_base, energy, r.M, spc, in.thr_lin, in.end_j, r.e, r.tgt, r.inavg, r.valid, r.jump0, r.Mp);
     return hipGetLastError();
 }

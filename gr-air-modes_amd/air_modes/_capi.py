@@ -170,16 +170,18 @@ class Library(object):
             getattr(L, name).argtypes = [vp, ci]
         for name in ("am_get_fix_errors", "am_pipe_get_fix_errors", "am_spipe_get_fix_errors"):
             getattr(L, name).argtypes = [vp]
-        for name in ("am_set_address_gate", "am_pipe_set_address_gate"):
+        for name in ("am_set_address_gate", "am_pipe_set_address_gate", "am_spipe_set_address_gate"):
             getattr(L, name).argtypes = [vp, ci, f64]
-        for name in ("am_get_address_gate", "am_pipe_get_address_gate"):
+        for name in ("am_get_address_gate", "am_pipe_get_address_gate", "am_spipe_get_address_gate"):
             getattr(L, name).argtypes = [vp, C.POINTER(ci), C.POINTER(f64)]
-        L.am_get_address_gate_stats.argtypes = [vp, pu64, pu64, pu64, pu64]
-        for name in ("am_set_address_repair", "am_pipe_set_address_repair"):
+        for name in ("am_get_address_gate_stats", "am_spipe_get_address_gate_stats"):
+            getattr(L, name).argtypes = [vp, pu64, pu64, pu64, pu64]
+        for name in ("am_set_address_repair", "am_pipe_set_address_repair", "am_spipe_set_address_repair"):
             getattr(L, name).argtypes = [vp, ci]
-        for name in ("am_get_address_repair", "am_pipe_get_address_repair"):
+        for name in ("am_get_address_repair", "am_pipe_get_address_repair", "am_spipe_get_address_repair"):
             getattr(L, name).argtypes = [vp]
-        L.am_get_address_repair_stats.argtypes = [vp, pu64, pu64]
+        for name in ("am_get_address_repair_stats", "am_spipe_get_address_repair_stats"):
+            getattr(L, name).argtypes = [vp, pu64, pu64]
         self.L = L
         if L.am_abi_version() != ABI_VERSION:
             raise OSError("ABI version mismatch in %s" % path)
@@ -854,6 +856,39 @@ class StreamPipe(object):
 
     def get_fix_errors(self):
         return int(self.lib.L.am_spipe_get_fix_errors(self._h))
+
+    def set_address_gate(self, mode, ttl=60.0):
+        """As Context.set_address_gate, for the pipe's ONE stream: the map is the pipe's, empty when a stream starts; the result
+        does not depend on the chunking, the depth or redone chunks.  With no chunk in flight."""
+        self._chk(self.lib.L.am_spipe_set_address_gate(self._h, int(mode), float(ttl)))
+
+    def get_address_gate(self):
+        """(mode, ttl in seconds)"""
+        mode, ttl = C.c_int(0), C.c_double(0.0)
+        self._chk(self.lib.L.am_spipe_get_address_gate(self._h, C.byref(mode), C.byref(ttl)))
+        return int(mode.value), float(ttl.value)
+
+    def address_gate_stats(self, not_learned=True):
+        """Since the pipe was created, of the chunks collected: dict(taught=, passed=, dropped=, not_learned=)
+        (am_spipe_get_address_gate_stats).  not_learned=False leaves that one out: it has to be fetched from the device."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        p = [C.byref(x) for x in v]
+        self._chk(self.lib.L.am_spipe_get_address_gate_stats(self._h, p[0], p[1], p[2], p[3] if not_learned else None))
+        names = ("taught", "passed", "dropped", "not_learned")[:4 if not_learned else 3]
+        return dict(zip(names, (int(x.value) for x in v)))
+
+    def set_address_repair(self, max_bits):
+        """As Context.set_address_repair, against the pipe's map; with no chunk in flight.  Inert while the gate is off."""
+        self._chk(self.lib.L.am_spipe_set_address_repair(self._h, int(max_bits)))
+
+    def get_address_repair(self):
+        return int(self.lib.L.am_spipe_get_address_repair(self._h))
+
+    def address_repair_stats(self):
+        """Since the pipe was created, of the chunks collected: dict(repaired=, ambiguous=)."""
+        v = [C.c_uint64(0), C.c_uint64(0)]
+        self._chk(self.lib.L.am_spipe_get_address_repair_stats(self._h, C.byref(v[0]), C.byref(v[1])))
+        return dict(repaired=int(v[0].value), ambiguous=int(v[1].value))
 
     def submit_device(self, ptr, n, flush=False):
         self._chk(self.lib.L.am_spipe_submit(self._h, int(ptr), int(n), AM_F_DEVICE_IN | (AM_F_FLUSH if flush else 0)))

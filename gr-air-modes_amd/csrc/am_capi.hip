@@ -133,6 +133,11 @@ struct am_ctx {
     int gate_repair = 0;          // 0: off; 1: on (inert while gate_mode is 0)
     DevBuf<uint32_t> gate_list;   // counters and the hit indices of the failed address/parity records (am_gate_args.rl)
     uint64_t repair_stat[2] = {0, 0};    // repaired, ambiguous since am_create (accepted scans only)
+    // am_spipe_set_address_gate: the context slices a chunk of a pipe's stream.  The map is the pipe's RUNNING map,
+    // not gate_map; the chunk's records enter it behind the chunk's own gate kernels, and those wait for the chunk before
+    unsigned long long *gate_pipe_map = nullptr;   // the pipe's (not owned); null: the context's own map and rules
+    hipEvent_t gate_wait = nullptr;                // the pipe's: behind the gate kernels of the chunk before (null: nothing to wait for)
+    hipEvent_t gate_done = nullptr;                // the pipe's: recorded behind this chunk's gate kernels, for the chunk behind it
     int tile = 0;
     // Speculative launches: the candidate count of a scan is only known on the device when its kernels
     // are enqueued.  Instead of a host round trip in the middle of the pipeline, the streaming path
@@ -738,9 +743,28 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
 }
 
 // ---- address gate: host side (am_set_address_gate) ----------------------------------------------------------------------
+constexpr size_t gate_map_bytes() { return ((size_t)4 + (size_t)2 * AM_GATE_MAP_SLOTS) * sizeof(unsigned long long); }
+
+// a map (the context's, or one of an am_spipe's two) as the gate's kernels are told of it: header, keys, last item counts
+void gate_point_at(am_gate_args &a, unsigned long long *map)
+{
+    a.t_hdr = map;
+    a.t_key = a.t_hdr + 4;
+    a.t_last = a.t_key + AM_GATE_MAP_SLOTS;
+    a.t_mask = AM_GATE_MAP_SLOTS - 1u;
+    a.t_limit = (unsigned long long)AM_GATE_MAP_SLOTS / 4 * 3;
+}
+
+// an emptied map keeps the counter of addresses not learned (the word behind the slots taken)
+hipError_t gate_map_empty(unsigned long long *map, hipStream_t s)
+{
+    hipError_t rc = hipMemsetAsync(map + 4, 0, (size_t)2 * AM_GATE_MAP_SLOTS * sizeof(unsigned long long), s);
+    return rc != hipSuccess ? rc : hipMemsetAsync(map, 0, sizeof(unsigned long long), s);
+}
+
 // Buffers and arguments for the gate over the n_max (or *n_ptr) records the next slicing launch writes: the record array (its
 // address goes into the context's scalar block, where am_slice_wave<FIX, 1> finds it), the call's table, the context's map
-// (zero when allocated) and, for K streams in one scan, their offsets and emit limits.
+// (zero when allocated; a chunk of am_spipe: the pipe's running map) and, for K streams in one scan, their offsets and emit limits.
 int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *packets)
 {
     am_gate_args &a = c->ga;
@@ -756,10 +780,9 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
     uint32_t slots = 64;
     while (slots < 2u * n_max) slots <<= 1;                  // (n_max < 2^31 / 240: no overflow)
     ENSURE(c, c->gate_scratch, am_gate_scratch_bytes(slots));
-    if (!c->gate_map.p) {
-        const size_t bytes = ((size_t)4 + (size_t)2 * AM_GATE_MAP_SLOTS) * sizeof(unsigned long long);
-        ENSURE(c, c->gate_map, bytes);
-        HIPCHK(c, hipMemsetAsync(c->gate_map.p, 0, bytes, c->stream));
+    if (!c->gate_pipe_map && !c->gate_map.p) {
+        ENSURE(c, c->gate_map, gate_map_bytes());
+        HIPCHK(c, hipMemsetAsync(c->gate_map.p, 0, gate_map_bytes(), c->stream));
     }
     am_gate_scratch_layout(a, c->gate_scratch.p, slots);
     a.rec = c->gate_rec.p;
@@ -770,11 +793,7 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
     if (c->gate_ttl < 1) c->gate_ttl = 1;
     a.ttl = c->gate_ttl;
     a.mode = c->gate_mode;
-    a.t_hdr = c->gate_map.p;
-    a.t_key = a.t_hdr + 4;
-    a.t_last = a.t_key + AM_GATE_MAP_SLOTS;
-    a.t_mask = AM_GATE_MAP_SLOTS - 1u;
-    a.t_limit = (unsigned long long)AM_GATE_MAP_SLOTS / 4 * 3;
+    gate_point_at(a, c->gate_pipe_map ? c->gate_pipe_map : c->gate_map.p);
     a.packets = packets;
     if (c->gate_repair) {
         ENSURE(c, c->gate_list, ((size_t)AM_GATE_RL_HDR + (n_max ? n_max : 1)) * sizeof(uint32_t));
@@ -963,14 +982,23 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
     else
         HIPCHK(c, am_launch_extract_slice(recs, {sc.ref.bb, c->frac ? c->chip_idx.p : nullptr, c->geom.hist0, req.e_off}, c->spc,
                                           c->emit_idx.p, stamp, so, c->stream));
-    if (gate) HIPCHK(c, am_launch_gate(c->ga, n_max, c->stream));     // behind the slicing launch, in front of the ticket
+    if (gate && c->gate_pipe_map) {
+        // a chunk of am_spipe: the running map must hold all the chunk before taught -- and, through it, all the
+        // chunks before that -- when this chunk's test reads it; what this chunk teaches enters it behind its own test and repair.
+        // Only the gate waits: the scan and the slicing above overlap with the chunk before as ever.
+        if (c->gate_wait) HIPCHK(c, hipStreamWaitEvent(c->stream, c->gate_wait, 0));
+        HIPCHK(c, am_launch_gate(c->ga, n_max, c->stream));
+        HIPCHK(c, am_launch_gate_commit_running(c->ga, c->stream));
+        if (c->gate_done) HIPCHK(c, hipEventRecord(c->gate_done, c->stream));     // (wait and record: one place; in front of the tail copy and the ticket)
+    } else if (gate)
+        HIPCHK(c, am_launch_gate(c->ga, n_max, c->stream));     // behind the slicing launch, in front of the ticket
     if (req.copy_tail)
         // time shards: the samples the next step needs in front of its chunk, kept while this step's are still in place
         // (am_shard_keep_tail; behind the extraction kernel, which still reads them; complete when the ticket is seen)
         HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
     const uint32_t seq = ++c->ticket_seq;
     if (gate)
-        HIPCHK(c, am_launch_gate_ticket(c->pin_scalars, seq, c->ga.cnt, c->ga.rl, c->stream));
+        HIPCHK(c, am_launch_gate_ticket(c->pin_scalars, seq, c->ga.cnt, c->ga.rl, c->stream, req.flag_src, req.word_src));
     else
         HIPCHK(c, am_launch_ticket(c->pin_scalars + AM_PW_TICKET, seq, c->stream, req.flag_src, req.flag_src ? c->pin_scalars + AM_PW_FLAG : nullptr,
                                    req.word_src, req.word_src ? reinterpret_cast<uint64_t *>(c->pin_scalars + AM_PW_EXIT) : nullptr));
@@ -1124,6 +1152,7 @@ bool resolve_plan(const am_ctx *c, const am_shard_exit *msgs, uint32_t world, ui
     req.base_abs = c->shard_base;
     req.max_hits = (uint32_t)((c->shard_end - c->shard_start + (uint64_t)c->spc) / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
     req.copy_tail = c->keep_bytes != 0;
+    req.gate = c->gate_mode != 0;                              // (only a context of am_spipe gets here with the gate on)
     if (msgs) {
         req.has_entry = true;
         req.entry = shard_entry_src(c, msgs, world, rank, msg_cap);
@@ -2120,7 +2149,7 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
 {
     if (!c) return AM_EINVAL;
     if (n_table) *n_table = 0;
-    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
+    // (the public calls refuse the gate; am_spipe, whose chunks are all on this GPU and share one map, comes here with it)
     if (abs_end < abs_start || abs_end > total_n) return fail(c, AM_EINVAL, "bad chunk bounds");
     HIPCHK(c, hipSetDevice(c->device));
     c->shard_ready = false;
@@ -2262,6 +2291,10 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
 int am_shard_scan(am_ctx *c, const float *iq, uint64_t abs_start, uint64_t abs_end, uint64_t total_n,
                   uint32_t flags, am_shard_exit *table, uint64_t cap, uint64_t *n_table)
 {
+    if (c && c->gate_mode) {
+        if (n_table) *n_table = 0;
+        return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
+    }
     return shard_scan_core(c, iq, abs_start, abs_end, total_n, flags, table, cap, n_table, nullptr, 0);
 }
 
@@ -2278,6 +2311,7 @@ int am_shard_scan_async(am_ctx *c, const float *iq, uint64_t abs_start, uint64_t
                         uint32_t flags, am_shard_exit *msg_dev, uint64_t msg_cap)
 {
     if (!c || !msg_dev || msg_cap == 0) return AM_EINVAL;
+    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (!device_addressable(msg_dev)) return fail(c, AM_EINVAL, "am_shard_scan_async: msg_dev is not device-addressable memory");
     return shard_scan_core(c, iq, abs_start, abs_end, total_n, flags, nullptr, 0, nullptr, msg_dev, msg_cap);
 }
@@ -2353,17 +2387,17 @@ int am_stream_copy(am_ctx *c, void *dst, const void *src, uint64_t nbytes)
     return AM_OK;
 }
 
-int am_shard_resolve(am_ctx *c, uint64_t cur_in, am_packet *out, uint64_t cap, uint64_t *n_out)
+// am_shard_resolve behind its refusal of the gate (am_spipe's redone chunk comes here with it)
+static int shard_resolve_sync(am_ctx *c, uint64_t cur_in, am_packet *out, uint64_t cap, uint64_t *n_out)
 {
-    if (!c) return AM_EINVAL;
-    if (n_out) *n_out = 0;
-    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (!c->shard_ready) return fail(c, AM_EINVAL, "am_shard_scan has not been called");
     HIPCHK(c, hipSetDevice(c->device));
     c->pending.clear();
     c->last_tags = 0;
     TailReq req;
     if (!resolve_plan(c, nullptr, 0, 0, 0, req)) {
+        c->gate_live = false;
+        c->n_hits = 0;
         if (c->keep_bytes) {                                    // (nothing to slice: the tail is still kept)
             HIPCHK(c, hipMemcpyAsync(c->keep_dst, c->keep_src, c->keep_bytes, hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2376,6 +2410,14 @@ int am_shard_resolve(am_ctx *c, uint64_t cur_in, am_packet *out, uint64_t cap, u
     if (rc != AM_OK) return rc;
     c->last_tags = c->n_hits;
     return hand_out(c, out, cap, n_out);
+}
+
+int am_shard_resolve(am_ctx *c, uint64_t cur_in, am_packet *out, uint64_t cap, uint64_t *n_out)
+{
+    if (!c) return AM_EINVAL;
+    if (n_out) *n_out = 0;
+    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
+    return shard_resolve_sync(c, cur_in, out, cap, n_out);
 }
 
 int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t world, uint32_t rank, uint64_t msg_cap,
@@ -2439,6 +2481,7 @@ struct am_spipe_slot {
     am_ctx *c = nullptr;
     am_shard_exit *msg = nullptr;       // device message of the chunk's scan: header + msg_cap entries
     hipEvent_t done = nullptr;          // behind the chunk's resolve step
+    hipEvent_t gate_done = nullptr;     // behind the chunk's gate kernels (created with the pipe's maps; recorded for every chunk)
     const float *iq = nullptr;          // the chunk as submitted
     uint64_t S = 0, n = 0;
     bool flush = false, first = false;
@@ -2457,6 +2500,14 @@ struct am_spipe {
     int prev_slot = -1;
     uint64_t redone = 0;                // chunks that went through the synchronous path
     std::vector<am_shard_exit> host_tab;
+    // am_spipe_set_address_gate / _repair: one stream, one map -- kept twice.  The RUNNING map is what the chunks in
+    // flight read and teach, in stream order (an event from chunk to chunk); the ACCEPTED map is taught only by chunks the host has
+    // collected, and is what the running map is put back to when a chunk is redone.  Nothing is allocated while the gate is off.
+    int gate_mode = 0, gate_repair = 0;
+    double gate_ttl_s = 60.0;
+    unsigned long long *gate_running = nullptr, *gate_accepted = nullptr;
+    bool gate_dirty = false;            // a gated chunk has been enqueued since the maps were last emptied
+    uint64_t gate_stat[3] = {0, 0, 0}, repair_stat[2] = {0, 0};   // of the chunks collected (never of a discarded attempt)
     const am_ctx *last_fail = nullptr;
     char err[160] = "";
 };
@@ -2496,6 +2547,8 @@ static int shard_resolve_enqueue(am_ctx *c, const am_shard_exit *msgs, uint32_t 
     TailReq req;
     if (!resolve_plan(c, msgs, world, rank, msg_cap, req)) {
         // nothing to slice: the entry is still composed (the chunk passes the scan position on), one ticket
+        c->gate_live = false;                                   // (no gate either: nothing of the chunk before in this context counts)
+        c->n_hits = 0;
         am_entry_src es = shard_entry_src(c, msgs, world, rank, msg_cap);
         es.cur_in = cur_in; es.carry_out = carry_out;
         HIPCHK(c, am_launch_shard_entry(es, cur0_dev, c->stream));
@@ -2545,6 +2598,65 @@ static int shard_resolve_complete(am_ctx *c, int *redo, uint64_t *exit_after)
     return AM_OK;
 }
 
+// the pipe's two maps and the slots' gate events, when the gate first runs
+static int spipe_gate_ensure(am_spipe *p, am_ctx *c)
+{
+    if (p->gate_running) return AM_OK;
+    for (am_spipe_slot &sl : p->slot)
+        if (!sl.gate_done) HIPCHK(c, hipEventCreateWithFlags(&sl.gate_done, hipEventDisableTiming));
+    // (gate_running, which says that all of this exists, is set last; am_spipe_destroy frees whatever a failure leaves)
+    if (!p->gate_accepted) HIPCHK(c, hipMalloc((void **)&p->gate_accepted, gate_map_bytes()));
+    // zeroed on the stream of the chunk that is about to use them, and waited for: no chunk is in flight here (the setting cannot
+    // change under chunks in flight), and every later chunk, on whatever stream, is enqueued after this wait
+    HIPCHK(c, hipMemsetAsync(p->gate_accepted, 0, gate_map_bytes(), c->stream));
+    unsigned long long *m = nullptr;
+    HIPCHK(c, hipMalloc((void **)&m, gate_map_bytes()));
+    hipError_t rc = hipMemsetAsync(m, 0, gate_map_bytes(), c->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(c->stream);
+    if (rc != hipSuccess) (void)hipFree(m);
+    HIPCHK(c, rc);
+    p->gate_running = m;
+    return AM_OK;
+}
+
+// the chunk in slot k has been ACCEPTED (collected, not redone): its teaches enter the accepted map, its counters the pipe's.
+// before[]: the context's five counters in front of the completion that accepted it
+static int spipe_gate_accept(am_spipe *p, size_t k, const uint64_t *before)
+{
+    am_spipe_slot &sl = p->slot[k];
+    am_ctx *c = sl.c;
+    if (!c->gate_live) return AM_OK;
+    for (int i = 0; i < 3; i++) p->gate_stat[i] += c->gate_stat[i] - before[i];
+    for (int i = 0; i < 2; i++) p->repair_stat[i] += c->repair_stat[i] - before[3 + i];
+    // (the stream's last chunk commits too, although the maps are emptied behind it: an address that does not fit is counted in
+    // not_learned for every chunk whose other counters count)
+    if (!c->n_hits) return AM_OK;
+    am_gate_args a = c->ga;
+    gate_point_at(a, p->gate_accepted);
+    a.n_ptr = nullptr;
+    a.n = c->n_hits;
+    HIPCHK(c, am_launch_gate_commit(a, c->stream));
+    c->tail_synced = false;
+    return AM_OK;
+}
+
+static void spipe_gate_counters(const am_ctx *c, uint64_t *v)
+{
+    for (int i = 0; i < 3; i++) v[i] = c->gate_stat[i];
+    for (int i = 0; i < 2; i++) v[3 + i] = c->repair_stat[i];
+}
+
+// The order of the gate goes from chunk to chunk on every path.  A chunk that ran the gate waited for the chunk before it and
+// recorded its own event around its gate kernels (chain_finish); a chunk without a gate launch of its own (nothing to slice) does
+// both here, so that the chunk behind it is ordered behind both.
+static int spipe_gate_pass_on(am_ctx *c)
+{
+    if (c->gate_live) return AM_OK;
+    if (c->gate_wait) HIPCHK(c, hipStreamWaitEvent(c->stream, c->gate_wait, 0));
+    HIPCHK(c, hipEventRecord(c->gate_done, c->stream));
+    return AM_OK;
+}
+
 // enqueue scan + resolve of the chunk in slot k (its fields are filled in); nothing waits
 static int spipe_enqueue(am_spipe *p, size_t k)
 {
@@ -2554,6 +2666,16 @@ static int spipe_enqueue(am_spipe *p, size_t k)
     uint64_t a0, a1, total;
     const float *ptr;
     spipe_bounds(p, sl, &a0, &a1, &total, &ptr);
+    c->gate_mode = p->gate_mode; c->gate_ttl_s = p->gate_ttl_s; c->gate_repair = p->gate_repair;
+    c->gate_wait = nullptr;
+    c->gate_done = nullptr;
+    if (p->gate_mode) {
+        if (int rcg = spipe_gate_ensure(p, c); rcg != AM_OK) return rcg;
+        c->gate_pipe_map = p->gate_running;
+        c->gate_done = sl.gate_done;
+        if (!sl.first && p->prev_slot >= 0) c->gate_wait = p->slot[(size_t)p->prev_slot].gate_done;
+        p->gate_dirty = true;
+    }
     // the samples in front of the chunk: the tail of the chunk before it, copied there unless the stream is contiguous in memory
     if (!sl.first && p->prev_iq) {
         const uint64_t front = p->hl + p->H;
@@ -2571,7 +2693,9 @@ static int spipe_enqueue(am_spipe *p, size_t k)
         cur_in = pv.c->shard_exit.p;
         HIPCHK(c, hipStreamWaitEvent(c->stream, pv.done, 0));
     }
-    return shard_resolve_enqueue(c, sl.msg, 1, 0, p->msg_cap, cur_in, nullptr, sl.done);
+    rc = shard_resolve_enqueue(c, sl.msg, 1, 0, p->msg_cap, cur_in, nullptr, sl.done);
+    if (rc != AM_OK || !p->gate_mode) return rc;
+    return spipe_gate_pass_on(c);
 }
 
 // wait for the chunk in slot k; its packets stay in the context's hand-out list.  *redo: the chunk must go through the synchronous path
@@ -2622,9 +2746,12 @@ void am_spipe_destroy(am_spipe *p)
         if (sl.c) { (void)hipSetDevice(sl.c->device); (void)hipStreamSynchronize(sl.c->stream); }
         if (sl.msg) (void)hipFree(sl.msg);
         if (sl.done) (void)hipEventDestroy(sl.done);
+        if (sl.gate_done) (void)hipEventDestroy(sl.gate_done);
         am_destroy(sl.c);
     }
     if (p->zero_dev) (void)hipFree(p->zero_dev);
+    if (p->gate_running) (void)hipFree(p->gate_running);
+    if (p->gate_accepted) (void)hipFree(p->gate_accepted);
     delete p;
 }
 
@@ -2659,6 +2786,61 @@ int am_spipe_set_fix_errors(am_spipe *p, int max_bits)
 }
 int am_spipe_get_fix_errors(const am_spipe *p) { return p && !p->slot.empty() ? p->slot[0].c->fix_bits : AM_EINVAL; }
 
+// The address gate for the pipe's one stream.  The setting is the pipe's and goes to a context with every chunk; the
+// maps are kept across a new setting, as am_set_address_gate keeps the context's.
+int am_spipe_set_address_gate(am_spipe *p, int mode, double ttl_seconds)
+{
+    if (!p) return AM_EINVAL;
+    if (mode < 0 || mode > 2) return spipe_fail(p, AM_EINVAL, "address_gate: mode must be 0, 1 or 2");
+    if (!std::isfinite(ttl_seconds) || !(ttl_seconds > 0.0)) return spipe_fail(p, AM_EINVAL, "address_gate: ttl must be finite and positive");
+    if (p->inflight) return spipe_fail(p, AM_EINVAL, "address_gate: collect the chunks in flight first");
+    p->gate_mode = mode;
+    p->gate_ttl_s = ttl_seconds;
+    return AM_OK;
+}
+int am_spipe_get_address_gate(const am_spipe *p, int *mode, double *ttl_seconds)
+{
+    if (!p) return AM_EINVAL;
+    if (mode) *mode = p->gate_mode;
+    if (ttl_seconds) *ttl_seconds = p->gate_ttl_s;
+    return AM_OK;
+}
+// (not_learned is counted where the accepted map is taught; fetched when somebody asks, behind every stream of the pipe)
+int am_spipe_get_address_gate_stats(const am_spipe *p, uint64_t *taught, uint64_t *passed, uint64_t *dropped, uint64_t *not_learned)
+{
+    if (!p) return AM_EINVAL;
+    if (taught) *taught = p->gate_stat[0];
+    if (passed) *passed = p->gate_stat[1];
+    if (dropped) *dropped = p->gate_stat[2];
+    if (not_learned) {
+        unsigned long long v = 0;
+        if (p->gate_accepted) {
+            if (hipSetDevice(p->slot[0].c->device) != hipSuccess) return AM_EHIP;
+            for (const am_spipe_slot &sl : p->slot)
+                if (hipStreamSynchronize(sl.c->stream) != hipSuccess) return AM_EHIP;
+            if (hipMemcpy(&v, p->gate_accepted + 1, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return AM_EHIP;
+        }
+        *not_learned = v;
+    }
+    return AM_OK;
+}
+int am_spipe_set_address_repair(am_spipe *p, int max_bits)
+{
+    if (!p) return AM_EINVAL;
+    if (max_bits < 0 || max_bits > 1) return spipe_fail(p, AM_EINVAL, "address_repair: max_bits must be 0 or 1");
+    if (p->inflight) return spipe_fail(p, AM_EINVAL, "address_repair: collect the chunks in flight first");
+    p->gate_repair = max_bits;
+    return AM_OK;
+}
+int am_spipe_get_address_repair(const am_spipe *p) { return p ? p->gate_repair : AM_EINVAL; }
+int am_spipe_get_address_repair_stats(const am_spipe *p, uint64_t *repaired, uint64_t *ambiguous)
+{
+    if (!p) return AM_EINVAL;
+    if (repaired) *repaired = p->repair_stat[0];
+    if (ambiguous) *ambiguous = p->repair_stat[1];
+    return AM_OK;
+}
+
 int am_spipe_submit(am_spipe *p, const float *iq, uint64_t n, uint32_t flags)
 {
     if (!p) return AM_EINVAL;
@@ -2691,6 +2873,8 @@ int am_spipe_collect(am_spipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
     if (c->pend.active) {
         int redo = 0;
         uint64_t leave = 0;
+        uint64_t gate_before[5];
+        spipe_gate_counters(c, gate_before);
         int rc = spipe_complete(p, k, &redo, &leave);
         if (rc != AM_OK) { p->last_fail = c; return rc; }
         if (redo) {
@@ -2706,18 +2890,30 @@ int am_spipe_collect(am_spipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
                 cj->pending.clear();
                 if (rc != AM_OK) { p->last_fail = cj; return rc; }
             }
+            p->last_fail = c;                                   // (should a HIP call below fail: the message is this context's)
+            if (p->gate_mode) {
+                // what this attempt and the chunks behind it taught the running map never happened: it becomes the accepted map
+                // again, which holds the chunks collected so far and nothing else (their commits may still be running on streams
+                // nothing was enqueued on since)
+                for (am_spipe_slot &s2 : p->slot) HIPCHK(c, hipStreamSynchronize(s2.c->stream));
+                HIPCHK(c, hipMemcpyAsync(p->gate_running, p->gate_accepted, gate_map_bytes(), hipMemcpyDeviceToDevice, c->stream));
+                c->gate_wait = nullptr;                         // (everything in front of this chunk has been collected)
+                spipe_gate_counters(c, gate_before);            // (the discarded attempt counts nothing)
+            }
             uint64_t a0, a1, total, m = 0;
             const float *ptr;
             spipe_bounds(p, sl, &a0, &a1, &total, &ptr);
-            rc = am_shard_scan(c, ptr, a0, a1, total, AM_F_DEVICE_IN | (sl.flush ? 0u : AM_F_MORE), p->host_tab.data(), p->host_tab.size(), &m);
+            rc = shard_scan_core(c, ptr, a0, a1, total, AM_F_DEVICE_IN | (sl.flush ? 0u : AM_F_MORE), p->host_tab.data(), p->host_tab.size(), &m, nullptr, 0);
             if (rc != AM_OK) { p->last_fail = c; return rc; }
             const am_shard_exit *tabs[1] = {p->host_tab.data()};
             uint64_t entry = 0;
             rc = am_shard_entry2(tabs, &m, 1, p->exit_host, &entry, &leave);
             if (rc != AM_OK) return spipe_fail(p, rc, "am_shard_entry2");
             uint64_t got = 0;
-            rc = am_shard_resolve(c, entry, nullptr, 0, &got);   // (the packets stay in the context's hand-out list: AM_ECAPACITY is expected)
+            rc = shard_resolve_sync(c, entry, nullptr, 0, &got);   // (the packets stay in the context's hand-out list: AM_ECAPACITY is expected)
             if (rc != AM_OK && rc != AM_ECAPACITY) { p->last_fail = c; return rc; }
+            if (p->gate_mode)                                   // (what the chunks submitted again wait for)
+                if (int grc = spipe_gate_pass_on(c); grc != AM_OK) return grc;
             rc = am_shard_set_exit(c, leave);
             if (rc != AM_OK) { p->last_fail = c; return rc; }
             // the chunks behind it, in order, once more (chunk k's own word now holds where the scan left it)
@@ -2734,6 +2930,8 @@ int am_spipe_collect(am_spipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
             p->prev_iq = piq; p->prev_n = pn; p->prev_slot = pslot;
         }
         p->exit_host = leave;
+        if (p->gate_mode)
+            if (int grc = spipe_gate_accept(p, k, gate_before); grc != AM_OK) { p->last_fail = c; return grc; }
     }
     const int hrc = hand_out(c, out, cap, n_out);
     if (hrc == AM_ECAPACITY) { p->last_fail = c; return hrc; }  // the packets stay: call again with a larger array
@@ -2742,6 +2940,20 @@ int am_spipe_collect(am_spipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
     if (p->ended && p->inflight == 0) {
         // the stream is over: the next submit starts a new one at sample 0
         for (am_spipe_slot &s2 : p->slot) { am_reset(s2.c); (void)am_shard_set_exit(s2.c, 0); }
+        if (p->gate_dirty) {
+            // ... and so is what the gate learned from it (the setting stays).  The accepted commit of a collected chunk runs on
+            // that chunk's own stream and nothing has waited for it: every stream of the pipe is synchronised HERE, before the
+            // memsets, so that no commit of the old stream can land in an emptied map (am_shard_set_exit above happens to wait
+            // for each stream too, but its result is not checked and the rule must not hang on it); then the memsets are waited
+            // for, so that the next stream's first chunk, on whatever stream, finds both maps empty
+            hipStream_t s0 = p->slot[0].c->stream;
+            bool ok = true;
+            for (am_spipe_slot &s2 : p->slot) ok = ok && hipStreamSynchronize(s2.c->stream) == hipSuccess;
+            if (!ok || gate_map_empty(p->gate_running, s0) != hipSuccess || gate_map_empty(p->gate_accepted, s0) != hipSuccess ||
+                hipStreamSynchronize(s0) != hipSuccess)
+                return spipe_fail(p, AM_EHIP, "address gate: the pipe's map could not be emptied");
+            p->gate_dirty = false;
+        }
         p->S_next = 0; p->ended = false; p->prev_iq = nullptr; p->prev_n = 0; p->prev_slot = -1; p->exit_host = 0;
     }
     return hrc;

@@ -212,11 +212,16 @@ __global__ void __launch_bounds__(256) am_k_gate_repair(am_gate_args a)
 }
 
 // the teaching records of a scan the host has accepted enter the context's map (one stream: never launched for K streams, whose
-// maps end with the call)
+// maps end with the call).  DEV_N = 1 (am_spipe, DESIGN.md 16): the chunk's records enter the pipe's RUNNING map as soon as the
+// chunk's own test and repair are through -- the count is still on the device (a.n is the bound the launch was sized for)
+template <int DEV_N>
 __global__ void __launch_bounds__(256) am_k_gate_commit(am_gate_args a)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
+    if constexpr (DEV_N > 0) {
+        const uint32_t n = *a.n_ptr;
+        if (i >= (n < a.n ? n : a.n)) return;
+    } else if (i >= a.n) return;
     const am_gate_rec r = a.rec[i];
     if (r.cls != AM_GC_TEACH) return;
     const unsigned long long key = (unsigned long long)r.addr + 1ull;
@@ -263,6 +268,24 @@ __global__ void am_k_gate_repair_ticket(uint32_t *host_word, uint32_t seq, const
     cnt_dst[AM_GATE_DST(AM_PW_AMBIGUOUS)] = rl[2];
     __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// ... and for a chunk of am_spipe, with what am_k_ticket carries for the pipe's resolve step: the redo flag and the word in which
+// the scan leaves the chunk (rl null: no repair)
+__global__ void am_k_gate_pipe_ticket(uint32_t *host_word, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl,
+                                      uint32_t *cnt_dst, const uint32_t *flag_src, uint32_t *flag_dst,
+                                      const unsigned long long *word_src, unsigned long long *word_dst)
+{
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_TAUGHT)] = (uint32_t)cnt[0];
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_PASSED)] = (uint32_t)cnt[1];
+    cnt_dst[AM_GATE_DST(AM_PW_GATE_DROPPED)] = (uint32_t)cnt[2];
+    if (rl) {
+        cnt_dst[AM_GATE_DST(AM_PW_REPAIRED)] = rl[1];
+        cnt_dst[AM_GATE_DST(AM_PW_AMBIGUOUS)] = rl[2];
+    }
+    if (flag_src) *flag_dst = *flag_src;
+    if (word_src) *word_dst = *word_src;
+    __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 #undef AM_GATE_DST
 
 size_t am_gate_scratch_bytes(uint32_t slots) { return ((size_t)4 + (size_t)3 * slots) * sizeof(unsigned long long); }
@@ -297,13 +320,26 @@ hipError_t am_launch_gate(const am_gate_args &a, uint32_t n_max, hipStream_t s)
 hipError_t am_launch_gate_commit(const am_gate_args &a, hipStream_t s)
 {
     if (a.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(am_k_gate_commit, dim3(am_grid(a.n, 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(am_k_gate_commit<0>, dim3(am_grid(a.n, 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t am_launch_gate_ticket(uint32_t *pin, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl, hipStream_t s)
+hipError_t am_launch_gate_commit_running(const am_gate_args &a, hipStream_t s)
+{
+    if (a.n == 0 || !a.n_ptr) return hipSuccess;
+    hipLaunchKernelGGL(am_k_gate_commit<1>, dim3(am_grid(a.n, 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t am_launch_gate_ticket(uint32_t *pin, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl, hipStream_t s,
+                                 const uint32_t *flag_src, const uint64_t *word_src)
 {
     uint32_t *host_word = pin + AM_PW_TICKET, *cnt_dst = pin + AM_PW_GATE_TAUGHT;
+    if (flag_src || word_src) {
+        hipLaunchKernelGGL(am_k_gate_pipe_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, rl, cnt_dst, flag_src, pin + AM_PW_FLAG,
+                           reinterpret_cast<const unsigned long long *>(word_src), reinterpret_cast<unsigned long long *>(pin + AM_PW_EXIT));
+        return hipGetLastError();
+    }
     if (rl) hipLaunchKernelGGL(am_k_gate_repair_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, rl, cnt_dst);
     else hipLaunchKernelGGL(am_k_gate_ticket, dim3(1), dim3(1), 0, s, host_word, seq, cnt, cnt_dst);
     return hipGetLastError();

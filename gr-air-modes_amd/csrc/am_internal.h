@@ -460,8 +460,12 @@ void am_gate_scratch_layout(am_gate_args &a, void *scratch, uint32_t slots);
 hipError_t am_launch_gate(const am_gate_args &a, uint32_t n_max, hipStream_t s);   /* zero the call's table, teach, test     */
                                                                                    /* (a.rl: and repair)                      */
 hipError_t am_launch_gate_commit(const am_gate_args &a, hipStream_t s);            /* a.n records of an ACCEPTED scan         */
+/* a chunk of am_spipe: the records a.n_ptr counts on the device (at most a.n) enter the map a.t_* at once  */
+hipError_t am_launch_gate_commit_running(const am_gate_args &a, hipStream_t s);
 /* the completion ticket of a gated scan.  pin: the context's pinned block -- pin[AM_PW_TICKET] = seq, pin[AM_PW_GATE_TAUGHT ..
- * AM_PW_GATE_DROPPED] = taught, passed, dropped; rl (a.rl, or null): pin[AM_PW_REPAIRED], pin[AM_PW_AMBIGUOUS] */
-hipError_t am_launch_gate_ticket(uint32_t *pin, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl, hipStream_t s);
+ * AM_PW_GATE_DROPPED] = taught, passed, dropped; rl (a.rl, or null): pin[AM_PW_REPAIRED], pin[AM_PW_AMBIGUOUS];
+ * flag_src / word_src (am_spipe; as am_launch_ticket's): these device words come along, to pin[AM_PW_FLAG] and pin[AM_PW_EXIT] */
+hipError_t am_launch_gate_ticket(uint32_t *pin, uint32_t seq, const unsigned long long *cnt, const uint32_t *rl, hipStream_t s,
+                                 const uint32_t *flag_src = nullptr, const uint64_t *word_src = nullptr);
 
 #endif

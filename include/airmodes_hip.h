@@ -188,9 +188,10 @@ AM_API int    am_get_fix_errors(const am_ctx *ctx);
  * am_submit_iq / am_collect and am_pipe_* (every batch is a whole stream with a map of its own), am_process_multi /
  * am_submit_multi / am_pipe_submit_multi (stream j of the K has a map of its own), am_slicer_work (the block alone: bursts in
  * ascending item counts; the context's map carries over from call to call until am_reset).  am_fetch_tags / am_last_num_tags
- * are about preamble hits and do not change.
- * NOT covered: am_spipe_* (chunks of one stream in flight on several contexts; no setter) and the time shards (the map would
- * have to cross ranks): with the gate on, am_shard_scan* / am_shard_resolve* return AM_ENOTSUP.
+ * are about preamble hits and do not change.  am_spipe_* (one stream, chunks in flight: the map is the pipe's) through
+ * am_spipe_set_address_gate below.
+ * NOT covered: the time shards (the map would have to cross ranks): with the gate on, am_shard_scan* / am_shard_resolve*
+ * return AM_ENOTSUP.
  * AM_EINVAL: mode outside 0..2, ttl_seconds not finite or <= 0.
  * Stats: since am_create, over all streams, of scans the library accepted (a speculative scan that had to be repeated counts
  * once): replies that taught, address/parity replies kept, packets dropped by the gate, addresses not learned.  Any pointer
@@ -222,7 +223,8 @@ AM_API int    am_get_address_gate_stats(const am_ctx *ctx, uint64_t *taught, uin
  * address/parity packet -- 2.6e-4 for 40 aircraft alive and a long reply, one in six for 25 000 -- so the repair is useless near
  * the map's capacity.  Nothing guards against it: the setting is for a receiver that hears a modest fleet.
  * The setting belongs to the context, survives am_reset and am_set_rate, takes effect with the next call and is inert while the
- * gate is off.  Covered: what the gate covers.  NOT covered: am_spipe_* and the time shards, as for the gate.
+ * gate is off.  Covered: what the gate covers (am_spipe_*: am_spipe_set_address_repair).  NOT covered: the time shards, as for
+ * the gate.
  * AM_EINVAL for max_bits outside 0..1.
  * Stats: since am_create, of scans the library accepted: packets repaired, packets dropped as ambiguous.  The gate's `dropped`
  * does not include a repaired packet; `passed` keeps its meaning (kept by step 2 as sliced).  Either pointer may be null. */
@@ -307,6 +309,26 @@ AM_API float am_spipe_last_kernel_ms(const am_spipe *pipe);   /* dominant-kernel
  * AM_EINVAL while chunks are in flight (as am_spipe_set_rx_time). */
 AM_API int am_spipe_set_fix_errors(am_spipe *pipe, int max_bits);
 AM_API int am_spipe_get_fix_errors(const am_spipe *pipe);
+/* Replaces: lib/slicer_impl.cc:170-182 as am_set_address_gate, for the pipe's ONE stream.  The packets of all chunks,
+ * concatenated in submission order, are those the pipe hands out with the gate off, filtered by the definition at
+ * am_set_address_gate (steps 1-3): whatever the chunk sizes, the depth, the memory layout, and whether a chunk had to be redone
+ * (am_spipe_redone) -- a redone chunk and the chunks submitted again behind it teach and count nothing from the attempt that was
+ * thrown away.  One stream, one map: it belongs to the pipe, is empty when a stream starts (first chunk after create, or after
+ * the AM_F_FLUSH chunk of the stream before has been collected), and item counts are the stream's.  A new mode or ttl keeps the
+ * map.  With mode 0 (default) the pipe allocates nothing for the gate and launches what it launches without it.
+ * AM_EINVAL: what am_set_address_gate refuses, and while chunks are in flight.
+ * Stats: since am_spipe_create, of the chunks collected (an AM_ECAPACITY from am_spipe_collect leaves the packets behind;
+ * collecting them later counts nothing twice).  Any pointer may be null; asking for not_learned waits for the pipe's streams. */
+AM_API int am_spipe_set_address_gate(am_spipe *pipe, int mode, double ttl_seconds);
+AM_API int am_spipe_get_address_gate(const am_spipe *pipe, int *mode, double *ttl_seconds);
+AM_API int am_spipe_get_address_gate_stats(const am_spipe *pipe, uint64_t *taught, uint64_t *passed, uint64_t *dropped,
+                                           uint64_t *not_learned);
+/* Replaces: nothing in the reference (lib/slicer_impl.cc:170-182 checks no parity here), as am_set_address_repair, for the
+ * pipe's stream and against the pipe's map; inert while the gate is off, and then nothing more is launched than the gate needs.
+ * AM_EINVAL for max_bits outside 0..1, and while chunks are in flight.  Stats as above: packets repaired, dropped as ambiguous. */
+AM_API int am_spipe_set_address_repair(am_spipe *pipe, int max_bits);
+AM_API int am_spipe_get_address_repair(const am_spipe *pipe);
+AM_API int am_spipe_get_address_repair_stats(const am_spipe *pipe, uint64_t *repaired, uint64_t *ambiguous);
 
 /* Run the context's device work on the caller's HIP stream (hipStream_t passed as a pointer; NULL: back to the
  * context's own stream).  For callers whose input is produced on a stream of their own -- e.g. halo samples that

@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from .modes_types import long_formats_mask
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(os.path.dirname(_HERE), "csrc", "libairmodes_hip.so")
 
@@ -23,6 +25,7 @@ ABI_VERSION = 5
 SHARD_MSG_HEADER = 2          # header entries of a device-side exit-table message (am_shard_scan_async)
 
 AM_OK, AM_EINVAL, AM_ENODEV, AM_ENOMEM, AM_EHIP, AM_ECAPACITY, AM_ENOTSUP = 0, -1, -2, -3, -4, -5, -6
+AM_LF_DF18, AM_LF_DF19 = 1, 2
 
 PACKET_DTYPE = np.dtype([
     ("data", "u1", 14), ("nbytes", "u1"), ("df", "u1"), ("numlowconf", "u1"),
@@ -180,6 +183,10 @@ class Library(object):
             getattr(L, name).argtypes = [vp, ci]
         for name in ("am_get_address_repair", "am_pipe_get_address_repair", "am_spipe_get_address_repair"):
             getattr(L, name).argtypes = [vp]
+        for name in ("am_set_long_formats", "am_pipe_set_long_formats", "am_spipe_set_long_formats"):
+            getattr(L, name).argtypes = [vp, ci]
+        for name in ("am_get_long_formats", "am_pipe_get_long_formats", "am_spipe_get_long_formats"):
+            getattr(L, name).argtypes = [vp]
         for name in ("am_get_address_repair_stats", "am_spipe_get_address_repair_stats"):
             getattr(L, name).argtypes = [vp, pu64, pu64]
         self.L = L
@@ -295,6 +302,14 @@ class Context(object):
 
     def get_fix_errors(self):
         return int(self.lib.L.am_get_fix_errors(self._h))
+
+    def set_long_formats(self, formats):
+        """Opt-in 112-bit slicing and parity check for DF18 / DF19 squitters (am_set_long_formats): an int mask (AM_LF_DF18 = 1,
+        AM_LF_DF19 = 2) or an iterable of 18 / 19; 0 = the reference's behaviour, which cuts both to 56 bits."""
+        self._chk(self.lib.L.am_set_long_formats(self._h, long_formats_mask(formats)))
+
+    def get_long_formats(self):
+        return int(self.lib.L.am_get_long_formats(self._h))
 
     def set_address_gate(self, mode, ttl=60.0):
         """Opt-in address gate (am_set_address_gate; 0 = the reference, lib/slicer_impl.cc:170-182): a DF0/4/5/16/20/21 reply is
@@ -741,6 +756,13 @@ class Pipe(object):
     def get_fix_errors(self):
         return int(self.lib.L.am_pipe_get_fix_errors(self._h))
 
+    def set_long_formats(self, formats):
+        """As Context.set_long_formats, for every context of the pipe; with no batch in flight."""
+        self._chk(self.lib.L.am_pipe_set_long_formats(self._h, long_formats_mask(formats)))
+
+    def get_long_formats(self):
+        return int(self.lib.L.am_pipe_get_long_formats(self._h))
+
     def set_address_gate(self, mode, ttl=60.0):
         """As Context.set_address_gate, for every context of the pipe (every batch is a whole stream: its own empty map); with
         no batch in flight."""
@@ -856,6 +878,13 @@ class StreamPipe(object):
 
     def get_fix_errors(self):
         return int(self.lib.L.am_spipe_get_fix_errors(self._h))
+
+    def set_long_formats(self, formats):
+        """As Context.set_long_formats, for the whole stream; with no chunk in flight."""
+        self._chk(self.lib.L.am_spipe_set_long_formats(self._h, long_formats_mask(formats)))
+
+    def get_long_formats(self):
+        return int(self.lib.L.am_spipe_get_long_formats(self._h))
 
     def set_address_gate(self, mode, ttl=60.0):
         """As Context.set_address_gate, for the pipe's ONE stream: the map is the pipe's, empty when a stream starts; the result

@@ -1,7 +1,7 @@
 """File-source subset of the reference's command-line receiver (apps/modes_rx:32-110,
 python/radio.py:90-118,221-234):
 
-    python -m air_modes.modes_rx -s capture.cf32 -r 2e6 [-T 7.0] [--no-pmf] [--fix-errors N] [--address-gate M] [--address-ttl S] [--address-repair N] [-l lat,lon] [-n] [--raw]
+    python -m air_modes.modes_rx -s capture.cf32 -r 2e6 [-T 7.0] [--no-pmf] [--fix-errors N] [--address-gate M] [--address-ttl S] [--address-repair N] [--long-formats 18,19] [-l lat,lon] [-n] [--raw]
     python -m air_modes.modes_rx -s rtlsdr.cu8 -r 2.4e6            (-f cu8 when the name does not say it)
 
 Reads a gr_complex file (interleaved little-endian float32 I,Q -- what
@@ -31,6 +31,17 @@ import numpy as np
 from . import formats, resample
 
 
+def _long_formats(text):
+    """'18', '19' or '18,19' -> the formats as a tuple (argparse type of --long-formats)."""
+    try:
+        formats = tuple(int(t) for t in text.split(",") if t.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected 18, 19 or 18,19, not %r" % text)
+    if not formats or any(f not in (18, 19) for f in formats):
+        raise argparse.ArgumentTypeError("expected 18, 19 or 18,19, not %r" % text)
+    return formats
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="modes_rx", description=__doc__.split("\n\n")[0])
     ap.add_argument("-s", "--source", required=True, help="sample file: gr_complex (cf32), or see -f")   # radio.py:94
@@ -55,6 +66,10 @@ def build_parser():
     ap.add_argument("--address-repair", type=int, choices=[0, 1], default=0,
                     help="with --address-gate: keep a reply the gate drops if flipping exactly one of its bits gives it the "
                     "address of an aircraft heard within --address-ttl [default=%(default)s]")
+    ap.add_argument("--long-formats", type=_long_formats, default=(), metavar="18,19",
+                    help="slice these downlink formats (18: non-transponder extended squitter, 19: military extended "
+                    "squitter) as 112 bits and check their parity, instead of cutting them to 56 bits as "
+                    "slicer_impl.cc:140 does [default: none]")
     ap.add_argument("-l", "--location", default=None, help="receiver position as lat,lon (enables range/bearing "
                     "and surface positions)")                                                            # modes_rx:40
     ap.add_argument("-n", "--no-print", action="store_true", help="do not print decoded reports")       # modes_rx:45
@@ -87,9 +102,9 @@ def main(argv=None, out=None):
         rx_rate, resampler = 4e6, resample.gpu_resampler(4e6 / args.rate)
     rx = rx_path(rx_rate, args.threshold, queue, use_pmf=args.pmf, use_dcblock=args.dcblock, fix_errors=args.fix_errors,
                  address_gate=args.address_gate, address_ttl=args.address_ttl,
-                 address_repair=args.address_repair)    # (below 4 Msps: the window runs at 4 Msps too)
+                 address_repair=args.address_repair, long_formats=args.long_formats)    # (below 4 Msps: the window runs at 4 Msps too)
     publisher = pubsub()
-    feed = make_parser(publisher)
+    feed = make_parser(publisher, long_formats=args.long_formats)
     my_position = [float(n) for n in args.location.split(",")] if args.location else None
     if not args.no_print and not args.raw:
         output_print(cpr_decoder(my_position), publisher, callback=lambda line: print(line, file=out))

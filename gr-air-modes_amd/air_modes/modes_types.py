@@ -1,5 +1,20 @@
 """Small value types shared by the message consumers (reference: python/modes_types.py:24-107)."""
+import numbers
 from collections import namedtuple
+
+
+def long_formats_mask(formats):
+    """am_set_long_formats' mask (1 = DF18, 2 = DF19) from an int mask or an iterable of downlink formats (18, 19): what the
+    receiver (rx_path(long_formats=...)) and the parser (make_parser(long_formats=...)) are given.  An int is passed through
+    as it is -- whoever takes the mask refuses one it does not know."""
+    if isinstance(formats, numbers.Integral):
+        return int(formats)
+    mask = 0
+    for df in formats:
+        if int(df) not in (18, 19):
+            raise ValueError("long_formats: only DF18 and DF19 can be enabled, not %r" % (df,))
+        mask |= 1 << (int(df) - 18)
+    return mask
 
 
 class stamp:

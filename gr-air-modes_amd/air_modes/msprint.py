@@ -17,6 +17,7 @@ _FS_TEXT = {1: " (aircraft is on the ground)", 2: " (AIRBORNE ALERT)", 3: " (GRO
 
 class output_print:
     HANDLED = (0, 4, 5, 11, 16, 17, 20, 21)
+    HANDLED_LONG = (18, 19)
 
     def __init__(self, cpr, publisher, callback=None):
         self._cpr = cpr
@@ -24,6 +25,9 @@ class output_print:
         self._fns = list(self.HANDLED)
         for df in self.HANDLED:
             publisher.subscribe("type%i_dl" % df, getattr(self, "handle%i" % df))
+        for df in self.HANDLED_LONG:      # (published only by make_parser(long_formats=...), and only when 112 bits long)
+            publisher.subscribe("type%i_dl" % df, getattr(self, "handle%i" % df))
+            self._fns.append(df)
         publisher.subscribe("modes_dl", self.catch_nohandler)
 
     @staticmethod
@@ -93,47 +97,70 @@ class output_print:
             return
         self._print(line)
 
-    def handle17(self, msg):
+    def _squitter(self, msg, df):
+        """The line of an extended squitter laid out as DF17: DF17 itself, and the long DF18 / DF19 ones below."""
         icao24 = msg.data["aa"]
         bdsreg = msg.data["me"].get_type()
         line = self.prefix(msg)
         try:
             if bdsreg == 0x08:
                 ident, typestring = _p.parseBDS08(msg.data)
-                line += "Type 17 BDS0,8 (ident) from %x type %s ident %s" % (icao24, typestring, ident)
+                line += "Type %i BDS0,8 (ident) from %x type %s ident %s" % (df, icao24, typestring, ident)
             elif bdsreg == 0x06:
                 track, lat, lon, rnge, bearing = _p.parseBDS06(msg.data, self._cpr)
-                line += "Type 17 BDS0,6 (surface report) from %x at (%.6f, %.6f) ground track %i" % (
-                    icao24, lat, lon, track)
+                line += "Type %i BDS0,6 (surface report) from %x at (%.6f, %.6f) ground track %i" % (
+                    df, icao24, lat, lon, track)
                 if rnge is not None and bearing is not None:
                     line += " (%.2f @ %.0f)" % (rnge, bearing)
             elif bdsreg == 0x05:
                 altitude, lat, lon, rnge, bearing = _p.parseBDS05(msg.data, self._cpr)
-                line += "Type 17 BDS0,5 (position report) from %x at (%.6f, %.6f)" % (icao24, lat, lon)
+                line += "Type %i BDS0,5 (position report) from %x at (%.6f, %.6f)" % (df, icao24, lat, lon)
                 if rnge is not None and bearing is not None:
                     line += " (%.2f @ %.0f)" % (rnge, bearing)
                 line += " at " + str(altitude) + "ft"
             elif bdsreg == 0x09:
                 subtype = msg.data["bds09"].get_type()
                 if subtype == 0:
-                    line += "Type 17 BDS0,9-%i (track report) from %x with velocity %.0fkt heading %.0f VS %.0f " \
-                            "turn rate %.0f" % ((subtype, icao24) + tuple(_p.parseBDS09_0(msg.data)))
+                    line += "Type %i BDS0,9-%i (track report) from %x with velocity %.0fkt heading %.0f VS %.0f " \
+                            "turn rate %.0f" % ((df, subtype, icao24) + tuple(_p.parseBDS09_0(msg.data)))
                 elif subtype == 1:
-                    line += "Type 17 BDS0,9-%i (track report) from %x with velocity %.0fkt heading %.0f VS %.0f" % (
-                        (subtype, icao24) + tuple(_p.parseBDS09_1(msg.data)))
+                    line += "Type %i BDS0,9-%i (track report) from %x with velocity %.0fkt heading %.0f VS %.0f" % (
+                        (df, subtype, icao24) + tuple(_p.parseBDS09_1(msg.data)))
                 elif subtype == 3:
                     mag_hdg, vel_src, vel, vert_spd, geo_diff = _p.parseBDS09_3(msg.data)
-                    line += "Type 17 BDS0,9-%i (air course report) from %x with %s %.0fkt magnetic heading %.0f " \
+                    line += "Type %i BDS0,9-%i (air course report) from %x with %s %.0fkt magnetic heading %.0f " \
                             "VS %.0f geo. diff. from baro. alt. %.0fft" % (
-                                subtype, icao24, vel_src, vel, mag_hdg, vert_spd, geo_diff)
+                                df, subtype, icao24, vel_src, vel, mag_hdg, vert_spd, geo_diff)
                 else:
-                    line += "Type 17 BDS0,9-%i from %x not implemented" % (subtype, icao24)
+                    line += "Type %i BDS0,9-%i from %x not implemented" % (df, subtype, icao24)
             else:
                 # (emergency status, register 0x61, lands here as well: the reference tests for 0x62)
-                line += "Type 17 with FTC=%i from %x not implemented" % (msg.data["ftc"], icao24)
+                line += "Type %i with FTC=%i from %x not implemented" % (df, msg.data["ftc"], icao24)
         except ADSBError:
             return
         self._print(line)
+
+    def handle17(self, msg):
+        self._squitter(msg, 17)
+
+    def handle18(self, msg):
+        """A 112-bit DF18 (rx_path(long_formats=...) and make_parser(long_formats=...); without the option, or 56 bits long,
+        it never gets here: parse.modes_reply has no table for it).  Control field 0, 1: ADS-B of a non-transponder device, 2, 5: TIS-B, 6: ADS-R -- the ME field is DF17's and the
+        position decoder is keyed by `aa`.  NOTE: with CF 1 and 5 `aa` is not an ICAO address (anonymous, or a track file
+        number): it may collide in the CPR cache with an aircraft that has the same 24 bits."""
+        cf = msg.data["cf"]
+        if cf in (0, 1, 2, 5, 6):
+            self._squitter(msg, 18)
+        else:
+            self._print(self.prefix(msg) + "Type 18 with CF=%i from %x not implemented" % (cf, msg.data["aa"]))
+
+    def handle19(self, msg):
+        """A 112-bit DF19: application field 0 is an extended squitter laid out as DF17; the others are the military's own."""
+        af = msg.data["af"]
+        if af == 0:
+            self._squitter(msg, 19)
+        else:
+            self._print(self.prefix(msg) + "Type 19 with AF=%i from %x not implemented" % (af, msg.data.get_bits(9, 24)))
 
     def printTCAS(self, msg):
         df = msg.data["df"]

@@ -13,7 +13,7 @@ import math
 
 from .altitude import decode_alt
 from .exceptions import ADSBError, FieldNotInPacket, NoHandlerError
-from .modes_types import modes_report, stamp
+from .modes_types import long_formats_mask, modes_report, stamp
 
 
 def _layout(spec, records=None):
@@ -52,12 +52,16 @@ class data_field:
             return 0
         return (self.data >> shift) & ((1 << num) - 1)
 
+    def layout(self):
+        """The field table of this record, None if its type has none."""
+        return self.dtypes.get(self.get_type())
+
     def parse(self):
-        kind = self.get_type()
-        if kind not in self.dtypes:
-            raise NoHandlerError(kind)
+        table = self.layout()
+        if table is None:
+            raise NoHandlerError(self.get_type())
         found = {}
-        for name, where in self.dtypes[kind].items():
+        for name, where in table.items():
             value = self.get_bits(where[0], where[1])
             if len(where) == 3:
                 value = where[2](value)
@@ -66,9 +70,8 @@ class data_field:
         return found
 
     def __getitem__(self, fieldname):
-        kind = self.get_type()
-        if kind not in self.dtypes:
-            raise NoHandlerError(kind)
+        if self.layout() is None:
+            raise NoHandlerError(self.get_type())
         if fieldname not in self.fields:
             raise FieldNotInPacket(fieldname)
         return self.fields[fieldname]
@@ -182,6 +185,28 @@ class modes_reply(data_field):
               20: _layout(_surv + " ac:20:13 mb:33:56:mb ap:88:24", {"mb": mb_reply}),
               21: _layout(_surv + " id:20:13 mb:33:56:mb ap:88:24", {"mb": mb_reply}),
               24: _layout("df:1:5 ke:6:1 nd:7:4 md:11:80 ap:88:24")}
+    # DF18 (extended squitter of a non-transponder device) and DF19 (military extended squitter) are 112 bits on the air, but the
+    # reference's slicer cuts them to 56 (lib/slicer_impl.cc:140) and its parser has no table for them.  These tables are opt-in
+    # like the slicing (am_set_long_formats): they are chosen only for a format in `long_formats` (the same mask: 1 = DF18,
+    # 2 = DF19) and only for a LONG message.  With the default 0 a DF18 / DF19 message of either length is what it always was
+    # to the reference's parser (no handler, nothing printed: its own vectors in tests/golden/parse_print.json hold 112-bit
+    # ones), and a 56-bit fragment is so with any mask.  DF19 with application field 0 is an extended squitter laid out as DF17; any other application field is the
+    # military's own.
+    long_dtypes = {18: _layout("df:1:5 cf:6:3 aa:9:24 me:33:56:me pi:88:24", {"me": me_reply}),
+                   19: _layout("df:1:5 af:6:3")}
+    _df19_es = _layout("df:1:5 af:6:3 aa:9:24 me:33:56:me pi:88:24", {"me": me_reply})
+
+    def __init__(self, data, long_formats=0):
+        self.long_formats = int(long_formats)
+        data_field.__init__(self, data)
+
+    def layout(self):
+        kind = self.get_type()
+        if kind in self.long_dtypes and (self.long_formats >> (kind - 18)) & 1 and self.is_long():
+            if kind == 19 and self.get_bits(6, 3) == 0:
+                return self._df19_es
+            return self.long_dtypes[kind]
+        return self.dtypes.get(kind)
 
     def is_long(self):
         return self.data > (1 << 56)
@@ -341,14 +366,20 @@ def parse_TCAS_CRM(data):
     return (res, comp, data["rat"], data["mte"])
 
 
-def make_parser(pub):
+def make_parser(pub, long_formats=0):
     """Returns the subscriber for the slicer's text messages ("<hex> <syndrome> <level> <secs>
     <frac>", slicer_impl.cc:176-193): parses one message and publishes the modes_report under
-    "modes_dl" and "type<DF>_dl" (parse.py:422-436).  Anything wrong with the frame is dropped."""
+    "modes_dl" and "type<DF>_dl" (parse.py:422-436).  Anything wrong with the frame is dropped.
+    `long_formats` is what the receiver was given (rx_path(long_formats=...): an int mask or an iterable of 18 / 19): the
+    112-bit messages of those formats are parsed and published, with the default none is, as in the reference."""
+    long_formats = long_formats_mask(long_formats)
+    if not 0 <= long_formats <= 3:
+        raise ValueError("long_formats: a mask of 1 (DF18) and 2 (DF19), not %r" % (long_formats,))
+
     def publish(message):
         data, ecc, reference, int_timestamp, frac_timestamp = message.split()
         try:
-            report = modes_report(modes_reply(int(data, 16)), int(ecc, 16),
+            report = modes_report(modes_reply(int(data, 16), long_formats), int(ecc, 16),
                                   10.0 * math.log10(max(1e-8, float(reference))),
                                   stamp(int(int_timestamp), float(frac_timestamp)))
             pub["modes_dl"] = report

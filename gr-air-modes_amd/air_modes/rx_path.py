@@ -14,7 +14,7 @@ from .blocks import slicer as _slicer
 
 class rx_path(object):
     def __init__(self, rate, threshold, queue, use_pmf=False, use_dcblock=False, device=-1, lib=None, fix_errors=0,
-                 address_gate=0, address_ttl=60.0, address_repair=0):
+                 address_gate=0, address_ttl=60.0, address_repair=0, long_formats=0):
         self._rate = int(rate)
         self._threshold = threshold
         self._queue = queue
@@ -32,6 +32,8 @@ class rx_path(object):
             self.set_fix_errors(fix_errors)
         if address_gate:
             self.set_address_gate(address_gate, address_ttl)
+        if long_formats:
+            self.set_long_formats(long_formats)
         if address_repair:
             self.set_address_repair(address_repair)
 
@@ -62,6 +64,15 @@ class rx_path(object):
 
     def get_fix_errors(self):
         return self._ctx.get_fix_errors()
+
+    # --- beyond the reference: it cuts DF18 / DF19 squitters, 112 bits on the air, to 56 (lib/slicer_impl.cc:140) ---
+    def set_long_formats(self, formats):
+        """From the next work() on, slice DF18 and / or DF19 as 112 bits and check their parity as DF17's (am_set_long_formats):
+        an int mask (1 = DF18, 2 = DF19) or an iterable of 18 / 19; 0 = off."""
+        self._ctx.set_long_formats(formats)
+
+    def get_long_formats(self):
+        return self._ctx.get_long_formats()
 
     # --- beyond the reference: it believes every address/parity reply, whatever its syndrome (lib/slicer_impl.cc:170-182) ---
     def set_address_gate(self, mode, ttl=60.0):
@@ -133,12 +144,14 @@ class rx_path_bank(object):
     of WHOLE streams (item counts and time stamps start at 0): the batch form of rx_path.work(capture, flush=True)."""
 
     def __init__(self, rate, threshold, queues, use_pmf=False, device=-1, lib=None, fix_errors=0, address_gate=0,
-                 address_ttl=60.0, address_repair=0):
+                 address_ttl=60.0, address_repair=0, long_formats=0):
         self._ctx = _capi.Context(float(int(rate)), float(threshold), use_pmf=use_pmf, device=device, lib=lib)
         if fix_errors:
             self._ctx.set_fix_errors(fix_errors)
         if address_gate:              # every receiver's capture is a stream of its own: a map per receiver
             self._ctx.set_address_gate(address_gate, address_ttl)
+        if long_formats:
+            self._ctx.set_long_formats(long_formats)
         if address_repair:            # receiver j's replies are searched in receiver j's map only
             self._ctx.set_address_repair(address_repair)
         self._slicers = [_slicer(q, _ctx=self._ctx) for q in queues]

@@ -116,6 +116,11 @@ struct am_ctx {
     float thr_lin = 0.0f;
     int use_pmf = 0;
     int fix_bits = 0;             // am_set_fix_errors: wrong bits a DF11 / DF17 reply may be repaired of (0: none, the reference's :179-182)
+    // am_set_long_formats: formats beyond the reference's four that are sliced as 112 bits (AM_LF_*).  The slicing
+    // kernels <FIX, GATE, 1> read them from scalars[AM_SW_LONG_FMT]; long_told is what that word holds (the block is zero when it
+    // is allocated), long_word the staging copy the host-to-device copy reads.
+    int long_mask = 0, long_told = 0;
+    uint32_t long_word = 0;
     // am_set_address_gate (kernels: am_gate.inc).  Nothing below is allocated or launched while gate_mode is 0.
     int gate_mode = 0;            // 0: off; 1: address/parity replies need a taught address; 2: and reserved formats are dropped
     double gate_ttl_s = 60.0;     // how long a taught address lives, seconds
@@ -332,6 +337,22 @@ int ensure_scalars(am_ctx *c)
     int rc = ensure(c, c->scalars, AM_SW_WORDS * sizeof(uint32_t));
     if (rc != AM_OK) return rc;
     if (hipMemsetAsync(c->scalars.p, 0, AM_SW_WORDS * sizeof(uint32_t), c->stream) != hipSuccess) return fail(c, AM_EHIP, "hipMemsetAsync");
+    return AM_OK;
+}
+
+// am_set_long_formats: the slicing launch that follows on the context's stream finds the enabled formats, as bits 18 and 19, in
+// scalars[AM_SW_LONG_FMT].  Written only when the setting has changed since the word was last written: a context that never had
+// the option on enqueues nothing here.
+int long_formats_tell(am_ctx *c)
+{
+    if (c->long_told == c->long_mask) return AM_OK;
+    if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
+    c->long_word = (uint32_t)c->long_mask << 18;
+    // (The source is pageable: the runtime copies so small a source into its own staging buffer before it returns, so the copy
+    // is ordered on the stream but not asynchronous to the host.  Nothing relies on either: long_word is a member, not a local,
+    // and changes only here, after the setter -- which the pipes refuse while work is in flight -- changed long_mask.)
+    HIPCHK(c, hipMemcpyAsync(c->scalars.p + AM_SW_LONG_FMT, &c->long_word, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    c->long_told = c->long_mask;
     return AM_OK;
 }
 
@@ -973,7 +994,8 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
     am_slice_out so;
     so.n_ptr = n_ptr; so.n_max = n_max; so.bursts_out = keep_dev ? c->bursts.p : nullptr; so.tags_out = keep_dev ? c->pin_tags : nullptr;
     so.crc_pow = c->crc_pow.p; so.packets = c->pin_packets; so.scalars = c->scalars.p; so.host_out = c->pin_scalars; so.Mp = Mp;
-    so.fix_bits = c->fix_bits; so.gate = slice_gate(c, gate);
+    so.fix_bits = c->fix_bits; so.gate = slice_gate(c, gate); so.long_mask = c->long_mask;
+    if (int rc = long_formats_tell(c); rc != AM_OK) return rc;
     const am_stamp stamp = {base_abs, c->rate_i, c->tt_dev.p, (uint32_t)c->tt.size()};
     if (sc.sparse && !keep_bursts)
         // bb exists only around the candidates: the 240 soft chips of a hit are recomputed from the scan's samples
@@ -1380,6 +1402,18 @@ int am_set_fix_errors(am_ctx *c, int max_bits)
     return AM_OK;
 }
 int am_get_fix_errors(const am_ctx *c) { return c ? c->fix_bits : AM_EINVAL; }
+
+// slicer_impl.cc:140 takes DF16/17/20/21 for long and cuts every other format to 56 bits, DF18 and DF19 among them.  The setting
+// selects the slicing kernels (am_slice_wave<FIX, GATE, LF>); the kernels read the enabled formats from the context's device block,
+// which the next slicing call writes on the context's stream in front of its launch (long_formats_tell).
+int am_set_long_formats(am_ctx *c, int mask)
+{
+    if (!c) return AM_EINVAL;
+    if (mask < 0 || mask > (AM_LF_DF18 | AM_LF_DF19)) return fail(c, AM_EINVAL, "long_formats: mask must be an OR of AM_LF_DF18 and AM_LF_DF19");
+    c->long_mask = mask;
+    return AM_OK;
+}
+int am_get_long_formats(const am_ctx *c) { return c ? c->long_mask : AM_EINVAL; }
 
 // slicer_impl.cc:170-182 checks parity for DF11 / DF17 only: in every other format the syndrome is "the address" and any bit
 // pattern passes.  The setting selects the slicing kernels (am_slice_wave<FIX, GATE>) and the gate launches behind them from the
@@ -2044,7 +2078,8 @@ int am_slicer_work(am_ctx *c, const float *bursts, const am_tag *tags, uint64_t 
     am_slice_out so;
     so.n_ptr = c->scalars.p + AM_SW_NBURSTS; so.n_max = nb32; so.bursts_out = nullptr; so.tags_out = nullptr;
     so.crc_pow = c->crc_pow.p; so.packets = c->packets.p; so.scalars = c->scalars.p; so.host_out = nullptr; so.Mp = nullptr;
-    so.fix_bits = c->fix_bits; so.gate = slice_gate(c, gate);
+    so.fix_bits = c->fix_bits; so.gate = slice_gate(c, gate); so.long_mask = c->long_mask;
+    if (int rc = long_formats_tell(c); rc != AM_OK) return rc;
     HIPCHK(c, am_launch_slice(c->bursts.p, c->tags.p, so, c->stream));
     unsigned long long gcnt[3] = {0, 0, 0};
     uint32_t rcnt[2] = {0, 0};
@@ -2786,6 +2821,17 @@ int am_spipe_set_fix_errors(am_spipe *p, int max_bits)
 }
 int am_spipe_get_fix_errors(const am_spipe *p) { return p && !p->slot.empty() ? p->slot[0].c->fix_bits : AM_EINVAL; }
 
+// (likewise; every context behind the pipe writes its own device word in front of its next slicing launch)
+int am_spipe_set_long_formats(am_spipe *p, int mask)
+{
+    if (!p) return AM_EINVAL;
+    if (mask < 0 || mask > (AM_LF_DF18 | AM_LF_DF19)) return spipe_fail(p, AM_EINVAL, "long_formats: mask must be an OR of AM_LF_DF18 and AM_LF_DF19");
+    if (p->inflight) return spipe_fail(p, AM_EINVAL, "long_formats: collect the chunks in flight first");
+    for (am_spipe_slot &sl : p->slot) sl.c->long_mask = mask;
+    return AM_OK;
+}
+int am_spipe_get_long_formats(const am_spipe *p) { return p && !p->slot.empty() ? p->slot[0].c->long_mask : AM_EINVAL; }
+
 // The address gate for the pipe's one stream.  The setting is the pipe's and goes to a context with every chunk; the
 // maps are kept across a new setting, as am_set_address_gate keeps the context's.
 int am_spipe_set_address_gate(am_spipe *p, int mode, double ttl_seconds)
@@ -3070,6 +3116,21 @@ int am_pipe_set_fix_errors(am_pipe *p, int max_bits)
     return AM_OK;
 }
 int am_pipe_get_fix_errors(const am_pipe *p) { return p && !p->sub.empty() ? p->sub[0]->fix_bits : AM_EINVAL; }
+
+// (likewise; every context behind the pipe writes its own device word in front of its next slicing launch)
+int am_pipe_set_long_formats(am_pipe *p, int mask)
+{
+    if (!p) return AM_EINVAL;
+    if (mask < 0 || mask > (AM_LF_DF18 | AM_LF_DF19) || p->inflight) {
+        p->last_fail = nullptr;
+        snprintf(p->err, sizeof(p->err), "%s", p->inflight ? "long_formats: collect the batches in flight first"
+                                                           : "long_formats: mask must be an OR of AM_LF_DF18 and AM_LF_DF19");
+        return AM_EINVAL;
+    }
+    for (am_ctx *c : p->sub) c->long_mask = mask;
+    return AM_OK;
+}
+int am_pipe_get_long_formats(const am_pipe *p) { return p && !p->sub.empty() ? p->sub[0]->long_mask : AM_EINVAL; }
 
 // (every batch is a whole stream: the map of the context that takes it is empty when it starts and is emptied when it ends)
 int am_pipe_set_address_gate(am_pipe *p, int mode, double ttl_seconds)

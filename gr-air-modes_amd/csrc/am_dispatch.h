@@ -1,6 +1,6 @@
 // am_dispatch.h -- which template instantiation a run-time value selects.  Plain C++17, no HIP: a host compiler builds it alone
 // (tests/helpers/dispatch_check.cc).  The launchers pass a generic lambda; it receives the values as std::integral_constant
-// and names the kernel with them: am_k_extract_slice<decltype(fix)::value, decltype(gate)::value>.
+// and names the kernel with them: am_k_extract_slice<decltype(fix)::value, decltype(gate)::value, decltype(lf)::value>.
 #ifndef AM_DISPATCH_H
 #define AM_DISPATCH_H
 
@@ -26,6 +26,17 @@ void am_with_fix_gate(int fix_bits, int gate, F &&f)
         else if (gate) f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
         else f(integral_constant<int, 2>{}, integral_constant<int, 0>{});
     }
+}
+
+// The slicing kernels <FIX, GATE, LF>: the same, and long_mask (am_set_long_formats): 0 = LF 0, the kernels as they are without
+// the option; anything else = LF 1, which reads the enabled formats from the context's device block.
+template <class F>
+void am_with_fix_gate_long(int fix_bits, int gate, int long_mask, F &&f)
+{
+    am_with_fix_gate(fix_bits, gate, [&](auto fix, auto g) {
+        if (long_mask) f(fix, g, std::integral_constant<int, 1>{});
+        else f(fix, g, std::integral_constant<int, 0>{});
+    });
 }
 
 // The samples per chip am_k_extract_slice_iq<SPC, ...> is instantiated for: the rates the streaming front ends serve.

@@ -5,7 +5,7 @@
 // How a launcher is called: what several launches share travels as one small struct, built where the context knows it --
 //   am_records      the resident candidate records and their count (every refinement, the chain, the extraction)
 //   am_emit_args    what the chain does with the candidates it visits; the marking kernels take it by value
-//   am_slice_out    what a slicing launch writes and which <FIX, GATE> instantiation runs (all three slicing launches)
+//   am_slice_out    what a slicing launch writes and which <FIX, GATE, LF> instantiation runs (all three slicing launches)
 //   am_stamp        the time tags of the two extraction launches
 // -- and a launcher has a struct of its own only for what is its alone (am_walk_req, am_dense_src, am_iq_src, ...).  A launcher that
 // takes one of them has no default arguments: an option nobody wants is written out as null or 0 at the call.  The launchers unpack the
@@ -45,6 +45,7 @@ enum am_scalar_word {            /* device block */
     AM_SW_CHAIN_ERR = 9,         /* a chained scan or the fused walk gave up waiting (am_chain_prefix, am_cblk_mark_body)         */
     AM_SW_TICKET_SCAN = 10,      /* ticket counter of am_k_exscan_chain (am_chain_place)                                          */
     AM_SW_TICKET_MARK = 11,      /* ... of the marking kernels                                                                    */
+    AM_SW_LONG_FMT = 12,         /* am_set_long_formats: bit 18 = DF18, bit 19 = DF19 is 112 bits long (am_slice_wave<.., .., 1>)  */
     AM_SW_GATE_REC = 14,         /* 64 bits, words 14..15: the address of the gate's record array (am_slice_wave<FIX, 1 or 2>)    */
     AM_SW_WORDS = 16
 };
@@ -75,7 +76,7 @@ constexpr bool am_word_map_ok(std::initializer_list<int> words, int size)   /* e
     return true;
 }
 static_assert(am_word_map_ok({AM_SW_RESUME, AM_SW_HIT, AM_SW_ENTRY, AM_SW_ENTRY_FLAG, AM_SW_CHAIN_ERR, AM_SW_TICKET_SCAN,
-                              AM_SW_TICKET_MARK, AM_SW_GATE_REC, AM_SW_GATE_REC + 1}, AM_SW_WORDS), "device block");
+                              AM_SW_TICKET_MARK, AM_SW_LONG_FMT, AM_SW_GATE_REC, AM_SW_GATE_REC + 1}, AM_SW_WORDS), "device block");
 static_assert(am_word_map_ok({AM_PW_HITS, AM_PW_RESUME, AM_PW_CANDIDATES, AM_PW_SHARD_COUNT, AM_PW_FLAG, AM_PW_CHAIN_ERR,
                               AM_PW_TICKET, AM_PW_GATE_TAUGHT, AM_PW_GATE_PASSED, AM_PW_GATE_DROPPED, AM_PW_EXIT, AM_PW_EXIT + 1,
                               AM_PW_REPAIRED, AM_PW_AMBIGUOUS}, AM_PW_WORDS), "pinned block");
@@ -372,9 +373,12 @@ struct am_time_tag {
  * gate: 1 = am_k_*<FIX, 1>, which also leaves an am_gate_rec per hit at the address in scalars[AM_SW_GATE_REC] (scalars must not be
  * null then); 2 = am_k_*<FIX, 2>: the same, and an address/parity record carries its DF (am_k_gate_repair); 0 = the kernels as they
  * are without the gate.
- * NO MEMBER HAS AN INITIALISER, and no site value-initialises one of these ("am_slice_out o = {};"): a silent 0 in fix_bits or
- * gate would run a scan without the repair and nobody would notice.  Each of the two sites that build one (chain_finish,
- * am_slicer_work) assigns all eleven members by name, in this order, so that a missing one shows when the site is read. */
+ * long_mask: am_set_long_formats' mask; non-zero = am_k_*<FIX, GATE, 1>, which reads the enabled formats from
+ * scalars[AM_SW_LONG_FMT] (the host has written them there on the same stream); 0 = the kernels as they are without the option.
+ * NO MEMBER HAS AN INITIALISER, and no site value-initialises one of these ("am_slice_out o = {};"): a silent 0 in fix_bits,
+ * gate or long_mask would run a scan without the option and nobody would notice.  Each of the two sites that build one
+ * (chain_finish, am_slicer_work) assigns all twelve members by name, in this order, so that a missing one shows when the site is
+ * read. */
 struct am_slice_out {
     const uint32_t *n_ptr;     /* device-side number of hits                                                     */
     uint32_t n_max;            /* upper bound used for the grid                                                  */
@@ -387,6 +391,7 @@ struct am_slice_out {
     const uint32_t *Mp;        /* or null: the scan's device-side candidate count, for host_out[AM_PW_CANDIDATES] */
     int fix_bits;
     int gate;
+    int long_mask;
 };
 /* the time tags of the extraction launches: tt[0..ntt) device array in ascending offset order */
 struct am_stamp {

@@ -2206,8 +2206,11 @@ __device__ __forceinline__ uint32_t am_bitrev8(uint32_t v)
 }
 
 // the slicer's long / short decision from the first five data bits of burst b (what am_slice_wave derives from its
-// ballots: slicer_impl.cc:128-140): callers that form the soft chips themselves skip chips 128.. of a short packet
-__device__ __forceinline__ bool am_burst_is_long(const float *b)
+// ballots: slicer_impl.cc:128-140): callers that form the soft chips themselves skip chips 128.. of a short packet.
+// LF = 1 (am_set_long_formats): lf_word = scalars[AM_SW_LONG_FMT], and the answer is am_slice_wave<FIX, GATE, 1>'s for every
+// header value -- a caller that disagreed would hand the wave a long packet whose second half was never formed.
+template <int LF>
+__device__ __forceinline__ bool am_burst_is_long(const float *b, uint32_t lf_word)
 {
     float s = b[0] + b[2];
     s = s + b[7];
@@ -2219,7 +2222,8 @@ __device__ __forceinline__ bool am_burst_is_long(const float *b)
     uint32_t hdr = 0;
 #pragma unroll
     for (int k = 0; k < 5; ++k) hdr = (hdr << 1) | (uint32_t)(am_chip_pair_slice(b[16 + 2 * k], b[17 + 2 * k], lo, hi, half_lo) & 1);
-    return hdr == 16 || hdr == 17 || hdr == 20 || hdr == 21;
+    if constexpr (LF > 0) return (((0x00330000u | lf_word) >> hdr) & 1u) != 0u;
+    else return hdr == 16 || hdr == 17 || hdr == 20 || hdr == 21;
 }
 
 // Repair of a DF11 / DF17 reply with one or two wrong bits (am_set_fix_errors).  The reference drops every such
@@ -2270,7 +2274,10 @@ __device__ __forceinline__ int am_fix_errors(unsigned long long &m0, unsigned lo
 // context keeps in scalars[AM_SW_GATE_REC] (device memory; a kernel argument of its own would change the <FIX, 0> kernels'
 // descriptors); 0 is the code as it was before the gate existed, and never looks at scalars.  2 (am_set_address_repair) = 1, and
 // the record of an address/parity reply carries its DF above the 24 bits of the syndrome.
-template <int FIX, int GATE>
+// LF: 1 = the formats am_set_long_formats enabled are 112 bits long, pass the parity test as DF17 does, are repaired as DF17
+// is and take no part in the gate.  Which formats: scalars[AM_SW_LONG_FMT], bit 18 for DF18 and bit 19 for DF19, one
+// wave-uniform load.  0 is the code as it was before the option existed, and never reads that word.
+template <int FIX, int GATE, int LF>
 __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, uint32_t i, int lane,
                                               const uint32_t *__restrict__ crc_pow, am_packet *__restrict__ packets,
                                               const uint32_t *__restrict__ scalars)
@@ -2291,7 +2298,14 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
     unsigned long long l0 = __ballot(!(r0 & 2));
     unsigned long long l1 = __ballot(!(r1 & 2));
     const uint32_t hdr = am_bitrev8((uint32_t)(m0 & 0x1Full)) >> 3;       // :135-139
-    const bool longpkt = (hdr == 16 || hdr == 17 || hdr == 20 || hdr == 21);   // :140
+    uint32_t lfw = 0u;                                                    // the enabled formats, as bits 18 and 19
+    bool longpkt;
+    if constexpr (LF > 0) {
+        lfw = scalars[AM_SW_LONG_FMT];
+        longpkt = (((0x00330000u | lfw) >> hdr) & 1u) != 0u;              // :140, and the enabled formats
+    } else {
+        longpkt = (hdr == 16 || hdr == 17 || hdr == 20 || hdr == 21);     // :140
+    }
     const int nbits = longpkt ? 112 : 56;
     if (!longpkt) {
         m0 &= (1ull << 56) - 1ull; m1 = 0ull;
@@ -2308,8 +2322,10 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
     if constexpr (FIX > 0) {
         // only where :182 below would drop the packet: DF11 / DF17 with a bad syndrome that passed :162-171 (DF11 is short and
         // DF17 long, so :170 never applies; the header bits are set, so :162-166 does not either).  (uniform)
-        if (part != 0 && (hdr == 17 || (hdr == 11 && nlow < 10)))
-            fixed = am_fix_errors(m0, m1, part, nbits, FIX >= 2 && hdr == 17, lane, crc_pow);
+        bool as17 = hdr == 17;                                           // (LF: an enabled format is treated as DF17 is)
+        if constexpr (LF > 0) as17 = (((1u << 17 | lfw) >> hdr) & 1u) != 0u;
+        if (part != 0 && (as17 || (hdr == 11 && nlow < 10)))
+            fixed = am_fix_errors(m0, m1, part, nbits, FIX >= 2 && as17, lane, crc_pow);
     }
     if (lane == 0) {
         am_packet p;
@@ -2319,7 +2335,11 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
         bool ok = (m0 | m1) != 0ull;                                         // :162-166
         if (!longpkt && mt != 11 && nlow > 0) ok = false;                    // :170
         if (mt == 11 && nlow >= 10) ok = false;                              // :171
-        if (part != 0 && (mt == 11 || mt == 17)) ok = false;                 // :182
+        if constexpr (LF > 0) {
+            if (part != 0 && ((((1u << 11 | 1u << 17) | lfw) >> mt) & 1u)) ok = false;   // :182, and the enabled formats
+        } else {
+            if (part != 0 && (mt == 11 || mt == 17)) ok = false;             // :182
+        }
         p.nbytes = (uint8_t)(nbits / 8);
         p.df = (uint8_t)mt;
         p.numlowconf = (uint8_t)nlow;
@@ -2334,7 +2354,9 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
             r.sample = t.sample;
             r.addr = part;
             r.cls = AM_GC_NONE;
-            if (ok) {
+            bool apart = false;                                               // an enabled long format: kept, teaches nothing, not tested
+            if constexpr (LF > 0) apart = ((lfw >> mt) & 1u) != 0u;
+            if (ok && !apart) {
                 if (mt == 11 || mt == 17) {                                   // (ok: the syndrome is 0, as sliced or repaired)
                     if (!fixed) {
                         r.cls = AM_GC_TEACH;
@@ -2367,8 +2389,10 @@ __device__ __forceinline__ void am_slice_wave(const float *b, const am_tag &t, u
 // profiles/fix_errors/isa_off_kernels.txt; how to make it again: README.md there.  Likewise GATE, the address gate
 // (am_set_address_gate): <FIX, 0> is instruction for instruction the kernel <FIX> from before the gate existed:
 // profiles/address_gate/isa_off_kernels.txt.  GATE = 2 (am_set_address_repair) is a third value, not a new argument: <FIX, 0> and
-// <FIX, 1> are the parent's kernels, profiles/address_repair/isa_off_kernels.txt.)
-template <int FIX, int GATE>
+// <FIX, 1> are the parent's kernels, profiles/address_repair/isa_off_kernels.txt.  Likewise LF, the long formats
+// (am_set_long_formats): <FIX, GATE, 0> is instruction for instruction the kernel <FIX, GATE> from before the option existed, takes
+// no new argument and never reads scalars[AM_SW_LONG_FMT]: profiles/long_formats/isa_off_kernels.txt.)
+template <int FIX, int GATE, int LF>
 __global__ void __launch_bounds__(256)
 am_k_slice(const float *__restrict__ bursts, const am_tag *__restrict__ tags, const uint32_t *__restrict__ n_ptr,
            const uint32_t *__restrict__ crc_pow, am_packet *__restrict__ packets,
@@ -2384,13 +2408,13 @@ am_k_slice(const float *__restrict__ bursts, const am_tag *__restrict__ tags, co
     }
     if (i >= *n_ptr) return;                              // wave-uniform; device-side burst count
     const am_tag t = tags[i];                             // (lane 0 uses it)
-    am_slice_wave<FIX, GATE>(bursts + (size_t)i * AM_BURST, t, i, lane, crc_pow, packets, scalars);
+    am_slice_wave<FIX, GATE, LF>(bursts + (size_t)i * AM_BURST, t, i, lane, crc_pow, packets, scalars);
 }
 
 // Extraction and slicing in one launch (the scan paths: every extracted burst is sliced right away).  One
 // wave per hit: the 240 soft chips go through LDS instead of a bursts[] round trip through memory; bursts_out
 // and tags_out are written only when the caller wants them (block-level API), packets as am_k_slice does.
-template <int FIX, int GATE>
+template <int FIX, int GATE, int LF>
 __global__ void __launch_bounds__(256)
 am_k_extract_slice(const float *__restrict__ bb, const float *__restrict__ inavg, int spc,
                    const int *__restrict__ chip_idx, int hist0,
@@ -2427,15 +2451,15 @@ am_k_extract_slice(const float *__restrict__ bb, const float *__restrict__ inavg
     t.how_late = e - pos[g];
     if (tags_out && lane == 0) tags_out[i] = t;
     __builtin_amdgcn_wave_barrier();                       // the wave's own LDS writes, in order, before its reads
-    am_slice_wave<FIX, GATE>(sb[wv], t, i, lane, crc_pow, packets, scalars);
+    am_slice_wave<FIX, GATE, LF>(sb[wv], t, i, lane, crc_pow, packets, scalars);
 }
 
 hipError_t am_launch_extract_slice(const am_records &r, const am_dense_src &src, int spc, const uint4 *emit_idx, const am_stamp &st,
                                    const am_slice_out &o, hipStream_t s)
 {
     if (o.n_max == 0) return hipSuccess;
-    am_with_fix_gate(o.fix_bits, o.gate, [&](auto fix, auto gate) {
-        hipLaunchKernelGGL((am_k_extract_slice<decltype(fix)::value, decltype(gate)::value>), dim3(am_grid(o.n_max, 4)), dim3(256), 0, s,
+    am_with_fix_gate_long(o.fix_bits, o.gate, o.long_mask, [&](auto fix, auto gate, auto lf) {
+        hipLaunchKernelGGL((am_k_extract_slice<decltype(fix)::value, decltype(gate)::value, decltype(lf)::value>), dim3(am_grid(o.n_max, 4)), dim3(256), 0, s,
                            src.bb, r.inavg, spc, src.chip_idx, src.hist0, emit_idx, o.n_ptr, r.pos, r.e, st.base_abs, src.e_off, st.rate,
                            st.tt, st.ntt, o.bursts_out, o.tags_out, o.crc_pow, o.packets, o.scalars, o.host_out, o.Mp);
     });
@@ -2615,7 +2639,7 @@ __device__ __forceinline__ float am_soft_chip_row32(const float *E, int row, int
 #ifndef AM_XS_WPS
 #define AM_XS_WPS 8                       /* waves per SIMD the extraction kernel is compiled for (64 VGPRs, no spills: eight workgroups per CU, 2 048 hits in flight) */
 #endif
-template <int SPC, int FIX, int GATE>
+template <int SPC, int FIX, int GATE, int LF>
 __global__ void __launch_bounds__(256, AM_XS_WPS)
 am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long long src_abs1, int use_pmf, float s1,
                       const float *__restrict__ inavg, const uint4 *__restrict__ emit_idx,
@@ -2646,6 +2670,8 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
     }
     const bool pmf = use_pmf != 0;
     const bool wide = (reinterpret_cast<uintptr_t>(iq) & 15u) == 0;
+    uint32_t lf_word = 0u;                                    // am_set_long_formats: the enabled formats (<..., 0> never reads them)
+    if constexpr (LF > 0) lf_word = scalars[AM_SW_LONG_FMT];
     // (Giving every XCD one contiguous eighth of the hits, so that the overlapping windows of neighbouring hits meet
     // in one L2, changed nothing: 56.3 against 56.7 us.  Budgeting the 64 Msps instantiation for six workgroups per CU
     // instead of five -- 80 VGPRs, 9 of them spilled -- 59 against 55 us, and 30-37 against 27 at 2 000 bursts/s.  Ten workgroups of two waves per CU instead of five of four --
@@ -2682,7 +2708,9 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
         }
         __syncthreads();
         AM_XSTAMP(1);
-        const bool all = bursts_out != nullptr || am_burst_is_long(sb);       // (uniform)
+        // (uniform; LF: the word the slicing wave reads below, so the two agree on every header value -- the staged rows and the
+        // direct loads of chips 128..239 both hang on `all`)
+        const bool all = bursts_out != nullptr || am_burst_is_long<LF>(sb, lf_word);
         if constexpr (SPC == 32) {
             if (staged && all) {                                              // (the rows' readers are behind the barrier above)
                 am_stage_energies32<(AM_BURST - HEAD) * 32>(iq, src_abs0, ae - (SPC - 1) + (long long)HEAD * SPC, stg, tid);
@@ -2705,7 +2733,7 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
             t.inavg = av;
             t.how_late = e - rec.y;
             if (tags_out && tid == 0) tags_out[i] = t;
-            am_slice_wave<FIX, GATE>(sb, t, i, lane, crc_pow, packets, scalars);
+            am_slice_wave<FIX, GATE, LF>(sb, t, i, lane, crc_pow, packets, scalars);
         }
         __syncthreads();                                          // (sb is rewritten by the next hit)
         AM_XSTAMP(3);
@@ -2721,7 +2749,7 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
 #endif
 }
 
-template <int SPC, int FIX, int GATE> struct am_xs_iq_key {};     // (names an instantiation's occupancy cache)
+template <int SPC, int FIX, int GATE, int LF> struct am_xs_iq_key {};     // (names an instantiation's occupancy cache)
 
 hipError_t am_launch_extract_slice_iq(const am_records &r, const am_iq_src &src, const uint4 *emit_idx, const am_stamp &st,
                                       const am_slice_out &o, hipStream_t s)
@@ -2731,21 +2759,21 @@ hipError_t am_launch_extract_slice_iq(const am_records &r, const am_iq_src &src,
     (void)hipGetDevice(&dev);
     const int use_pmf = src.spc == 1 ? 0 : src.use_pmf;       // (a one-sample window is the sample itself: s1 = 1)
     const bool known = am_with_spc(src.spc, [&](auto spc) {
-        am_with_fix_gate(o.fix_bits, o.gate, [&](auto fix, auto gate) {
-            constexpr int S = decltype(spc)::value, F = decltype(fix)::value, G = decltype(gate)::value;
+        am_with_fix_gate_long(o.fix_bits, o.gate, o.long_mask, [&](auto fix, auto gate, auto lf) {
+            constexpr int S = decltype(spc)::value, F = decltype(fix)::value, G = decltype(gate)::value, L = decltype(lf)::value;
             // workgroups of 256 threads per CU: what the instantiation's registers allow (five at 32 samples per chip, where a
             // lane holds a 34-sample window; eight at one or two samples per chip, where the kernel is a chain of memory round
             // trips per hit and more hits in flight is all that helps), asked of the runtime once per device and instantiation
-            std::atomic<int> *cached = am_device_cache<am_xs_iq_key<S, F, G>>(dev);
+            std::atomic<int> *cached = am_device_cache<am_xs_iq_key<S, F, G, L>>(dev);
             int w = cached ? cached->load(std::memory_order_acquire) : 0;
             if (w <= 0) {
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, F, G>), 256, 0) != hipSuccess || w <= 0) w = 5;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, F, G, L>), 256, 0) != hipSuccess || w <= 0) w = 5;
                 w = w > 8 ? 8 : w;
                 if (cached) cached->store(w, std::memory_order_release);
             }
             const uint32_t resident = (uint32_t)w * (uint32_t)am_device_cus();
             const uint32_t grid = o.n_max < resident ? o.n_max : resident;
-            hipLaunchKernelGGL((am_k_extract_slice_iq<S, F, G>), dim3(grid), dim3(256), 0, s, src.iq, src.src_abs0, src.src_abs1, use_pmf,
+            hipLaunchKernelGGL((am_k_extract_slice_iq<S, F, G, L>), dim3(grid), dim3(256), 0, s, src.iq, src.src_abs0, src.src_abs1, use_pmf,
                                src.s1, r.inavg, emit_idx, o.n_ptr, r.pos, r.e, st.base_abs, st.rate, st.tt, st.ntt, o.bursts_out,
                                o.tags_out, o.crc_pow, o.packets, o.scalars, o.host_out, o.Mp);
         });
@@ -2779,8 +2807,8 @@ hipError_t am_launch_ticket(uint32_t *host_word, uint32_t seq, hipStream_t s, co
 hipError_t am_launch_slice(const float *bursts, const am_tag *tags, const am_slice_out &o, hipStream_t s)
 {
     if (o.n_max == 0) return hipSuccess;
-    am_with_fix_gate(o.fix_bits, o.gate, [&](auto fix, auto gate) {
-        hipLaunchKernelGGL((am_k_slice<decltype(fix)::value, decltype(gate)::value>), dim3(am_grid(o.n_max, 4)), dim3(256), 0, s, bursts,
+    am_with_fix_gate_long(o.fix_bits, o.gate, o.long_mask, [&](auto fix, auto gate, auto lf) {
+        hipLaunchKernelGGL((am_k_slice<decltype(fix)::value, decltype(gate)::value, decltype(lf)::value>), dim3(am_grid(o.n_max, 4)), dim3(256), 0, s, bursts,
                            tags, o.n_ptr, o.crc_pow, o.packets, o.scalars, o.host_out, o.Mp);
     });
     return hipGetLastError();

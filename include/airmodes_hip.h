@@ -231,6 +231,34 @@ AM_API int    am_get_address_gate_stats(const am_ctx *ctx, uint64_t *taught, uin
 AM_API int    am_set_address_repair(am_ctx *ctx, int max_bits);
 AM_API int    am_get_address_repair(const am_ctx *ctx);
 AM_API int    am_get_address_repair_stats(const am_ctx *ctx, uint64_t *repaired, uint64_t *ambiguous);
+/* ---- opt-in 112-bit slicing and parity check for DF18 / DF19 squitters ------------------------------------------------
+ * Replaces: lib/slicer_impl.cc:140, which takes a reply for long iff its first five bits read 16, 17, 20 or 21.  DF18 (the
+ *           extended squitter of everything that is not a transponder: TIS-B, ADS-R, ground vehicles, obstacles) and DF19 (the
+ *           military extended squitter) are 112 bits on the air; the reference cuts them to 56, and what is left usually dies
+ *           at :170 or prints "No handler for message type 18".
+ * mask = 0 (default): the reference's behaviour -- every packet, message text and kernel is what it is without this call.
+ * mask = OR of AM_LF_DF18, AM_LF_DF19: with E the enabled formats and hdr the five header bits as sliced (:135-139),
+ *   length:  long iff hdr is 16, 17, 20, 21 or in E.  Everything from :142 to :171 runs with that length: all 112 decisions are
+ *            taken, the low-confidence count runs over 112 bits, and :170 (short packets only) does not apply to a format in E.
+ *   parity:  (:182) the packet is dropped if the syndrome is non-zero and DF is 11, 17 or in E: DF18 and DF19 carry a plain PI
+ *            field like DF17.  A DF19 whose application field uses another parity FAILS CLOSED: it is dropped, not handed out
+ *            unchecked.
+ *   repair:  with am_set_fix_errors a format in E gets exactly what DF17 gets -- one bit, and two bits at max_bits = 2, candidates
+ *            5..111, the DF bits never touched.
+ *   gate:    a kept packet of a format in E takes no part in the address gate: it is kept in mode 1 and in mode 2, teaches
+ *            nothing (non-transponders send no address/parity replies, and TIS-B addresses need not be ICAO) and is not
+ *            tested -- the class a repaired DF17 has.  A format not in E stays with the "others" of step 3 there.  The address
+ *            repair is unaffected.
+ *   packet:  nbytes = 14, df = 18 or 19, crc = 0; reserved[1] as for DF17.
+ * The preamble scan does not depend on any of this (it skips 240 chips after a hit whatever the length): hits, tags and
+ * am_fetch_tags are unchanged, and the packets of every format outside E are byte for byte what they are with mask 0
+ * (tests/longfmt_common.py restates the definition in numpy).
+ * The setting belongs to the context, survives am_reset and am_set_rate, takes effect with the next call and covers every call
+ * that slices (the list at am_set_fix_errors, the am_shard_resolve* calls included).  AM_EINVAL for a mask outside 0..3. */
+#define AM_LF_DF18 1
+#define AM_LF_DF19 2
+AM_API int    am_set_long_formats(am_ctx *ctx, int mask);
+AM_API int    am_get_long_formats(const am_ctx *ctx);
 /* ---- batches in flight ---------------------------------------------------------------------------------------
  * Under GNU Radio every block of rx_path runs in its own thread, so the slicer works on burst k while the preamble
  * block scans ahead (thread-per-block scheduler; python/rx_path.py wires five blocks).  The counterpart here: the
@@ -273,6 +301,10 @@ AM_API int am_pipe_get_address_gate(const am_pipe *pipe, int *mode, double *ttl_
  * outside 0..1. */
 AM_API int am_pipe_set_address_repair(am_pipe *pipe, int max_bits);
 AM_API int am_pipe_get_address_repair(const am_pipe *pipe);
+/* Replaces: lib/slicer_impl.cc:140 as am_set_long_formats, for every context behind the handle.  AM_EINVAL while batches are
+ * in flight, and for a mask outside 0..3. */
+AM_API int am_pipe_set_long_formats(am_pipe *pipe, int mask);
+AM_API int am_pipe_get_long_formats(const am_pipe *pipe);
 
 /* ---- ONE continuing stream with several of its chunks in flight ---------------------------------------------------
  * The reference's preamble block is a streaming block: general_work() resumes where the last call stopped (lib/preamble_impl.cc:
@@ -309,6 +341,10 @@ AM_API float am_spipe_last_kernel_ms(const am_spipe *pipe);   /* dominant-kernel
  * AM_EINVAL while chunks are in flight (as am_spipe_set_rx_time). */
 AM_API int am_spipe_set_fix_errors(am_spipe *pipe, int max_bits);
 AM_API int am_spipe_get_fix_errors(const am_spipe *pipe);
+/* Replaces: lib/slicer_impl.cc:140 as am_set_long_formats, for the whole stream.  AM_EINVAL while chunks are in flight, and
+ * for a mask outside 0..3. */
+AM_API int am_spipe_set_long_formats(am_spipe *pipe, int mask);
+AM_API int am_spipe_get_long_formats(const am_spipe *pipe);
 /* Replaces: lib/slicer_impl.cc:170-182 as am_set_address_gate, for the pipe's ONE stream.  The packets of all chunks,
  * concatenated in submission order, are those the pipe hands out with the gate off, filtered by the definition at
  * am_set_address_gate (steps 1-3): whatever the chunk sizes, the depth, the memory layout, and whether a chunk had to be redone

@@ -54,8 +54,10 @@ DF_MIX_EDGE = ((17, 0.20), (11, 0.15), (16, 0.15), (18, 0.15), (19, 0.10), (24, 
 
 
 def synth_capture(rate, n, lam, seed, sigma=0.01, snr_db=(10.0, 35.0), cfo_hz=50e3,
-                  overlap_frac=0.02, df_mix=DF_MIX, dtype=np.complex64):
+                  overlap_frac=0.02, df_mix=DF_MIX, dtype=np.complex64, frame_fn=make_frame):
     """n complex samples at `rate` (multiple of 2 MHz) with Poisson(lam per second) bursts.
+    frame_fn(rng, df) -> bytes makes every frame (make_frame: it must draw from rng what make_frame draws, or the capture
+    behind the first frame moves).
 
     Returns (iq complex64[n], truth) where truth is a list of dicts
     {start (float sample), frame (hex), snr_db}."""
@@ -85,7 +87,7 @@ def synth_capture(rate, n, lam, seed, sigma=0.01, snr_db=(10.0, 35.0), cfo_hz=50
     truth = []
     for t0 in starts:
         df = int(rng.choice(dfs, p=probs))
-        frame = make_frame(rng, df)
+        frame = frame_fn(rng, df)
         snr = float(rng.uniform(*snr_db))
         amp = np.sqrt(2.0) * sigma * 10.0 ** (snr / 20.0)
         phase = float(rng.uniform(0, 2 * np.pi))

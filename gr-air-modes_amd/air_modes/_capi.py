@@ -38,6 +38,21 @@ CAND_DTYPE = EXIT_DTYPE   # (name kept for older imports)
 assert PACKET_DTYPE.itemsize == 56 and TAG_DTYPE.itemsize == 32 and CAND_DTYPE.itemsize == 16
 
 
+# The opt-in decode options of the C ABI: (call, its argument types behind the handle, the handle kinds that have it).  The
+# same four options exist for am_ctx, am_pipe and am_spipe under these prefixes; am_pipe keeps no statistics.
+_HANDLES = ("am_", "am_pipe_", "am_spipe_")
+_pu64 = C.POINTER(C.c_uint64)
+_OPTION_CALLS = (
+    ("set_fix_errors", (C.c_int,), _HANDLES), ("get_fix_errors", (), _HANDLES),
+    ("set_long_formats", (C.c_int,), _HANDLES), ("get_long_formats", (), _HANDLES),
+    ("set_address_gate", (C.c_int, C.c_double), _HANDLES),
+    ("get_address_gate", (C.POINTER(C.c_int), C.POINTER(C.c_double)), _HANDLES),
+    ("set_address_repair", (C.c_int,), _HANDLES), ("get_address_repair", (), _HANDLES),
+    ("get_address_gate_stats", (_pu64,) * 4, ("am_", "am_spipe_")),
+    ("get_address_repair_stats", (_pu64,) * 2, ("am_", "am_spipe_")),
+)
+
+
 class AirModesError(RuntimeError):
     def __init__(self, code, text):
         RuntimeError.__init__(self, "airmodes_hip error %d: %s" % (code, text))
@@ -169,26 +184,9 @@ class Library(object):
         L.am_unpack.argtypes = [vp, vp, u64, ci, u32, vp]
         L.am_synchronize.argtypes = [vp]
         L.am_process_samples.argtypes = [vp, vp, u64, ci, u32, vp, u64, pu64]
-        for name in ("am_set_fix_errors", "am_pipe_set_fix_errors", "am_spipe_set_fix_errors"):
-            getattr(L, name).argtypes = [vp, ci]
-        for name in ("am_get_fix_errors", "am_pipe_get_fix_errors", "am_spipe_get_fix_errors"):
-            getattr(L, name).argtypes = [vp]
-        for name in ("am_set_address_gate", "am_pipe_set_address_gate", "am_spipe_set_address_gate"):
-            getattr(L, name).argtypes = [vp, ci, f64]
-        for name in ("am_get_address_gate", "am_pipe_get_address_gate", "am_spipe_get_address_gate"):
-            getattr(L, name).argtypes = [vp, C.POINTER(ci), C.POINTER(f64)]
-        for name in ("am_get_address_gate_stats", "am_spipe_get_address_gate_stats"):
-            getattr(L, name).argtypes = [vp, pu64, pu64, pu64, pu64]
-        for name in ("am_set_address_repair", "am_pipe_set_address_repair", "am_spipe_set_address_repair"):
-            getattr(L, name).argtypes = [vp, ci]
-        for name in ("am_get_address_repair", "am_pipe_get_address_repair", "am_spipe_get_address_repair"):
-            getattr(L, name).argtypes = [vp]
-        for name in ("am_set_long_formats", "am_pipe_set_long_formats", "am_spipe_set_long_formats"):
-            getattr(L, name).argtypes = [vp, ci]
-        for name in ("am_get_long_formats", "am_pipe_get_long_formats", "am_spipe_get_long_formats"):
-            getattr(L, name).argtypes = [vp]
-        for name in ("am_get_address_repair_stats", "am_spipe_get_address_repair_stats"):
-            getattr(L, name).argtypes = [vp, pu64, pu64]
+        for name, args, prefixes in _OPTION_CALLS:
+            for prefix in prefixes:
+                getattr(L, prefix + name).argtypes = [vp] + list(args)
         self.L = L
         if L.am_abi_version() != ABI_VERSION:
             raise OSError("ABI version mismatch in %s" % path)
@@ -248,7 +246,91 @@ def _iq_f32(iq):
     return np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
 
 
-class Context(object):
+class _DecodeOptions(object):
+    """The four opt-in decode options, for whichever handle the class wraps: _prefix names its C calls, _h is the handle, _chk
+    raises AirModesError with the handle's message.  `options_apply` says when a new setting is taken and when it is refused."""
+
+    _prefix = "am_"
+    options_apply = "from the next call on"
+
+    def _option(self, name, *args):
+        return getattr(self.lib.L, self._prefix + name)(self._h, *args)
+
+    def set_fix_errors(self, max_bits):
+        """Opt-in repair of DF11 / DF17 replies with up to max_bits (0, 1, 2) wrong bits (am_set_fix_errors; 0 = the
+        reference's drop, lib/slicer_impl.cc:179-182).  A repaired packet has crc 0 and reserved[1] = bits flipped.
+        Applies as the class's `options_apply` says."""
+        self._chk(self._option("set_fix_errors", int(max_bits)))
+
+    def get_fix_errors(self):
+        return int(self._option("get_fix_errors"))
+
+    def set_long_formats(self, formats):
+        """Opt-in 112-bit slicing and parity check for DF18 / DF19 squitters (am_set_long_formats): an int mask (AM_LF_DF18 = 1,
+        AM_LF_DF19 = 2) or an iterable of 18 / 19; 0 = the reference's behaviour, which cuts both to 56 bits.
+        Applies as the class's `options_apply` says."""
+        self._chk(self._option("set_long_formats", long_formats_mask(formats)))
+
+    def get_long_formats(self):
+        return int(self._option("get_long_formats"))
+
+    def set_address_gate(self, mode, ttl=60.0):
+        """Opt-in address gate (am_set_address_gate; 0 = the reference, lib/slicer_impl.cc:170-182): a DF0/4/5/16/20/21 reply is
+        handed out only if a parity-clean DF11 / DF17 reply taught its address at most ttl seconds of samples before it;
+        mode 2 also drops the formats that are neither.  Applies as the class's `options_apply` says."""
+        self._chk(self._option("set_address_gate", int(mode), float(ttl)))
+
+    def get_address_gate(self):
+        """(mode, ttl in seconds)"""
+        mode, ttl = C.c_int(0), C.c_double(0.0)
+        self._chk(self._option("get_address_gate", C.byref(mode), C.byref(ttl)))
+        return int(mode.value), float(ttl.value)
+
+    def set_address_repair(self, max_bits):
+        """Opt-in repair behind the address gate (am_set_address_repair; 0 = off, 1): an address/parity reply the gate drops is
+        kept if flipping exactly one of its bits 5.. makes its syndrome an address that is alive; it comes out with that bit
+        flipped, crc = the address and reserved[1] = 1.  Inert while the gate is off.  Applies as the class's `options_apply`
+        says."""
+        self._chk(self._option("set_address_repair", int(max_bits)))
+
+    def get_address_repair(self):
+        return int(self._option("get_address_repair"))
+
+
+class _DecodeStats(object):
+    """What the gate and its repair have counted since the handle was created -- for the handles whose ABI keeps the counters
+    (am_ctx: of the scans it accepted; am_spipe: of the chunks collected)."""
+
+    def address_gate_stats(self, not_learned=True):
+        """dict(taught=, passed=, dropped=, not_learned=) (am_get_address_gate_stats).  not_learned=False leaves that one out:
+        it is the only one that has to be fetched from the device."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        p = [C.byref(x) for x in v]
+        self._chk(self._option("get_address_gate_stats", p[0], p[1], p[2], p[3] if not_learned else None))
+        names = ("taught", "passed", "dropped", "not_learned")[:4 if not_learned else 3]
+        return dict(zip(names, (int(x.value) for x in v)))
+
+    def address_repair_stats(self):
+        """dict(repaired=, ambiguous=) (am_get_address_repair_stats)."""
+        v = [C.c_uint64(0), C.c_uint64(0)]
+        self._chk(self._option("get_address_repair_stats", C.byref(v[0]), C.byref(v[1])))
+        return dict(repaired=int(v[0].value), ambiguous=int(v[1].value))
+
+
+def apply_decode_options(target, fix_errors=0, address_gate=0, address_ttl=60.0, address_repair=0, long_formats=0):
+    """The constructor keywords of rx_path / rx_path_bank (and of anything else with the set_* methods above): every option that
+    is asked for is set on target, the others are left at their defaults."""
+    if fix_errors:
+        target.set_fix_errors(fix_errors)
+    if address_gate:
+        target.set_address_gate(address_gate, address_ttl)
+    if long_formats:
+        target.set_long_formats(long_formats)
+    if address_repair:
+        target.set_address_repair(address_repair)
+
+
+class Context(_DecodeOptions, _DecodeStats):
     """am_ctx wrapper: one receive path (one stream) on one GPU."""
 
     def __init__(self, rate, threshold_db=7.0, use_pmf=True, use_dcblock=False, device=-1, lib=None):
@@ -294,58 +376,6 @@ class Context(object):
 
     def get_pmf(self):
         return bool(self.lib.L.am_get_pmf(self._h))
-
-    def set_fix_errors(self, max_bits):
-        """Opt-in repair of DF11 / DF17 replies with up to max_bits (0, 1, 2) wrong bits (am_set_fix_errors; 0 = the
-        reference's drop, lib/slicer_impl.cc:179-182).  A repaired packet has crc 0 and reserved[1] = bits flipped."""
-        self._chk(self.lib.L.am_set_fix_errors(self._h, int(max_bits)))
-
-    def get_fix_errors(self):
-        return int(self.lib.L.am_get_fix_errors(self._h))
-
-    def set_long_formats(self, formats):
-        """Opt-in 112-bit slicing and parity check for DF18 / DF19 squitters (am_set_long_formats): an int mask (AM_LF_DF18 = 1,
-        AM_LF_DF19 = 2) or an iterable of 18 / 19; 0 = the reference's behaviour, which cuts both to 56 bits."""
-        self._chk(self.lib.L.am_set_long_formats(self._h, long_formats_mask(formats)))
-
-    def get_long_formats(self):
-        return int(self.lib.L.am_get_long_formats(self._h))
-
-    def set_address_gate(self, mode, ttl=60.0):
-        """Opt-in address gate (am_set_address_gate; 0 = the reference, lib/slicer_impl.cc:170-182): a DF0/4/5/16/20/21 reply is
-        handed out only if a parity-clean DF11 / DF17 reply taught its address at most ttl seconds of samples before it;
-        mode 2 also drops the formats that are neither."""
-        self._chk(self.lib.L.am_set_address_gate(self._h, int(mode), float(ttl)))
-
-    def get_address_gate(self):
-        """(mode, ttl in seconds)"""
-        mode, ttl = C.c_int(0), C.c_double(0.0)
-        self._chk(self.lib.L.am_get_address_gate(self._h, C.byref(mode), C.byref(ttl)))
-        return int(mode.value), float(ttl.value)
-
-    def address_gate_stats(self, not_learned=True):
-        """Since the context was created: dict(taught=, passed=, dropped=, not_learned=) (am_get_address_gate_stats).
-        not_learned=False leaves that one out: it is the only one that has to be fetched from the device."""
-        v = [C.c_uint64(0) for _ in range(4)]
-        p = [C.byref(x) for x in v]
-        self._chk(self.lib.L.am_get_address_gate_stats(self._h, p[0], p[1], p[2], p[3] if not_learned else None))
-        names = ("taught", "passed", "dropped", "not_learned")[:4 if not_learned else 3]
-        return dict(zip(names, (int(x.value) for x in v)))
-
-    def set_address_repair(self, max_bits):
-        """Opt-in repair behind the address gate (am_set_address_repair; 0 = off, 1): an address/parity reply the gate drops is
-        kept if flipping exactly one of its bits 5.. makes its syndrome an address that is alive; it comes out with that bit
-        flipped, crc = the address and reserved[1] = 1.  Inert while the gate is off."""
-        self._chk(self.lib.L.am_set_address_repair(self._h, int(max_bits)))
-
-    def get_address_repair(self):
-        return int(self.lib.L.am_get_address_repair(self._h))
-
-    def address_repair_stats(self):
-        """Since the context was created: dict(repaired=, ambiguous=) (am_get_address_repair_stats)."""
-        v = [C.c_uint64(0), C.c_uint64(0)]
-        self._chk(self.lib.L.am_get_address_repair_stats(self._h, C.byref(v[0]), C.byref(v[1])))
-        return dict(repaired=int(v[0].value), ambiguous=int(v[1].value))
 
     def reset(self):
         self._chk(self.lib.L.am_reset(self._h))
@@ -714,9 +744,13 @@ class Context(object):
         return self._received(out, got.value)
 
 
-class Pipe(object):
+class Pipe(_DecodeOptions):
     """am_pipe wrapper: `depth` contexts used round-robin by one host thread; independent batches (each a whole
     stream) are submitted and collected in order, the tail of one overlapping the front end of the next."""
+
+    _prefix = "am_pipe_"
+    options_apply = ("to every batch submitted from now on (every batch is a whole stream: the address gate starts it with an "
+                     "empty map); refused with AM_EINVAL while a batch is in flight")
 
     def __init__(self, rate, threshold_db=7.0, use_pmf=True, use_dcblock=False, device=-1, depth=3, lib=None):
         self.lib = lib or default_library()
@@ -748,37 +782,6 @@ class Pipe(object):
     def _chk(self, rc):
         if rc != AM_OK:
             raise AirModesError(rc, self.lib.L.am_pipe_last_error(self._h).decode())
-
-    def set_fix_errors(self, max_bits):
-        """As Context.set_fix_errors, for every context of the pipe; with no batch in flight."""
-        self._chk(self.lib.L.am_pipe_set_fix_errors(self._h, int(max_bits)))
-
-    def get_fix_errors(self):
-        return int(self.lib.L.am_pipe_get_fix_errors(self._h))
-
-    def set_long_formats(self, formats):
-        """As Context.set_long_formats, for every context of the pipe; with no batch in flight."""
-        self._chk(self.lib.L.am_pipe_set_long_formats(self._h, long_formats_mask(formats)))
-
-    def get_long_formats(self):
-        return int(self.lib.L.am_pipe_get_long_formats(self._h))
-
-    def set_address_gate(self, mode, ttl=60.0):
-        """As Context.set_address_gate, for every context of the pipe (every batch is a whole stream: its own empty map); with
-        no batch in flight."""
-        self._chk(self.lib.L.am_pipe_set_address_gate(self._h, int(mode), float(ttl)))
-
-    def get_address_gate(self):
-        mode, ttl = C.c_int(0), C.c_double(0.0)
-        self._chk(self.lib.L.am_pipe_get_address_gate(self._h, C.byref(mode), C.byref(ttl)))
-        return int(mode.value), float(ttl.value)
-
-    def set_address_repair(self, max_bits):
-        """As Context.set_address_repair, for every context of the pipe; with no batch in flight."""
-        self._chk(self.lib.L.am_pipe_set_address_repair(self._h, int(max_bits)))
-
-    def get_address_repair(self):
-        return int(self.lib.L.am_pipe_get_address_repair(self._h))
 
     def submit(self, iq):
         """A batch in host memory.  The samples must stay valid until the batch is collected: the (possibly converted)
@@ -824,12 +827,17 @@ class Pipe(object):
         return float(self.lib.L.am_pipe_last_kernel_ms(self._h))
 
 
-class StreamPipe(object):
+class StreamPipe(_DecodeOptions, _DecodeStats):
     """am_spipe wrapper: ONE continuing stream with `depth` of its consecutive chunks in flight on one GPU (lib/preamble_impl.cc:
     139-246 is a streaming block).  Chunks are DEVICE pointers; every chunk but a stream's first needs front() samples of room in
     front of it in the same allocation (the library copies the previous chunk's tail there unless the stream is contiguous in
     memory); a chunk and the one submitted before it stay valid until it is collected.  Packets of all chunks in order == one
     process_iq over the whole stream."""
+
+    _prefix = "am_spipe_"
+    options_apply = ("to the pipe's ONE stream, from the next chunk submitted on (the address gate's map is the pipe's, empty when "
+                     "a stream starts and kept across a new setting: the result does not depend on the chunking, the depth or "
+                     "redone chunks); refused with AM_EINVAL while a chunk is in flight")
 
     def __init__(self, rate, threshold_db=7.0, use_pmf=True, use_dcblock=False, device=-1, depth=3, lib=None):
         self.lib = lib or default_library()
@@ -871,53 +879,6 @@ class StreamPipe(object):
 
     def set_rx_time(self, offset, secs, frac):
         self._chk(self.lib.L.am_spipe_set_rx_time(self._h, int(offset), int(secs), float(frac)))
-
-    def set_fix_errors(self, max_bits):
-        """As Context.set_fix_errors, for the whole stream; with no chunk in flight."""
-        self._chk(self.lib.L.am_spipe_set_fix_errors(self._h, int(max_bits)))
-
-    def get_fix_errors(self):
-        return int(self.lib.L.am_spipe_get_fix_errors(self._h))
-
-    def set_long_formats(self, formats):
-        """As Context.set_long_formats, for the whole stream; with no chunk in flight."""
-        self._chk(self.lib.L.am_spipe_set_long_formats(self._h, long_formats_mask(formats)))
-
-    def get_long_formats(self):
-        return int(self.lib.L.am_spipe_get_long_formats(self._h))
-
-    def set_address_gate(self, mode, ttl=60.0):
-        """As Context.set_address_gate, for the pipe's ONE stream: the map is the pipe's, empty when a stream starts; the result
-        does not depend on the chunking, the depth or redone chunks.  With no chunk in flight."""
-        self._chk(self.lib.L.am_spipe_set_address_gate(self._h, int(mode), float(ttl)))
-
-    def get_address_gate(self):
-        """(mode, ttl in seconds)"""
-        mode, ttl = C.c_int(0), C.c_double(0.0)
-        self._chk(self.lib.L.am_spipe_get_address_gate(self._h, C.byref(mode), C.byref(ttl)))
-        return int(mode.value), float(ttl.value)
-
-    def address_gate_stats(self, not_learned=True):
-        """Since the pipe was created, of the chunks collected: dict(taught=, passed=, dropped=, not_learned=)
-        (am_spipe_get_address_gate_stats).  not_learned=False leaves that one out: it has to be fetched from the device."""
-        v = [C.c_uint64(0) for _ in range(4)]
-        p = [C.byref(x) for x in v]
-        self._chk(self.lib.L.am_spipe_get_address_gate_stats(self._h, p[0], p[1], p[2], p[3] if not_learned else None))
-        names = ("taught", "passed", "dropped", "not_learned")[:4 if not_learned else 3]
-        return dict(zip(names, (int(x.value) for x in v)))
-
-    def set_address_repair(self, max_bits):
-        """As Context.set_address_repair, against the pipe's map; with no chunk in flight.  Inert while the gate is off."""
-        self._chk(self.lib.L.am_spipe_set_address_repair(self._h, int(max_bits)))
-
-    def get_address_repair(self):
-        return int(self.lib.L.am_spipe_get_address_repair(self._h))
-
-    def address_repair_stats(self):
-        """Since the pipe was created, of the chunks collected: dict(repaired=, ambiguous=)."""
-        v = [C.c_uint64(0), C.c_uint64(0)]
-        self._chk(self.lib.L.am_spipe_get_address_repair_stats(self._h, C.byref(v[0]), C.byref(v[1])))
-        return dict(repaired=int(v[0].value), ambiguous=int(v[1].value))
 
     def submit_device(self, ptr, n, flush=False):
         self._chk(self.lib.L.am_spipe_submit(self._h, int(ptr), int(n), AM_F_DEVICE_IN | (AM_F_FLUSH if flush else 0)))

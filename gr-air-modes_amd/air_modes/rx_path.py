@@ -28,14 +28,8 @@ class rx_path(object):
         self._gate_used = False
         self.gated = 0                # packets the address gate dropped so far (set_address_gate); they are not in `packets`
         self.samples = 0
-        if fix_errors:
-            self.set_fix_errors(fix_errors)
-        if address_gate:
-            self.set_address_gate(address_gate, address_ttl)
-        if long_formats:
-            self.set_long_formats(long_formats)
-        if address_repair:
-            self.set_address_repair(address_repair)
+        # (through this object's own setters: set_address_gate notes that `gated` has to be kept)
+        _capi.apply_decode_options(self, fix_errors, address_gate, address_ttl, address_repair, long_formats)
 
     # --- reference surface: python/rx_path.py:67-87 ---
     def set_rate(self, rate):
@@ -146,14 +140,9 @@ class rx_path_bank(object):
     def __init__(self, rate, threshold, queues, use_pmf=False, device=-1, lib=None, fix_errors=0, address_gate=0,
                  address_ttl=60.0, address_repair=0, long_formats=0):
         self._ctx = _capi.Context(float(int(rate)), float(threshold), use_pmf=use_pmf, device=device, lib=lib)
-        if fix_errors:
-            self._ctx.set_fix_errors(fix_errors)
-        if address_gate:              # every receiver's capture is a stream of its own: a map per receiver
-            self._ctx.set_address_gate(address_gate, address_ttl)
-        if long_formats:
-            self._ctx.set_long_formats(long_formats)
-        if address_repair:            # receiver j's replies are searched in receiver j's map only
-            self._ctx.set_address_repair(address_repair)
+        # (every receiver's capture is a stream of its own: a gate map per receiver, and receiver j's replies are searched in
+        # receiver j's map only)
+        _capi.apply_decode_options(self._ctx, fix_errors, address_gate, address_ttl, address_repair, long_formats)
         self._slicers = [_slicer(q, _ctx=self._ctx) for q in queues]
         self.packets = [0] * len(queues)
 

@@ -6,6 +6,7 @@
 //   doubling)  ->  ordered compaction  ->  burst extraction  ->  slicer + CRC.
 // There is no CPU fallback: every entry point that computes needs a HIP device.
 #include "am_internal.h"
+#include "am_options.h"
 
 #include <chrono>
 #include <cmath>
@@ -89,7 +90,7 @@ struct TailReq {
     bool keep_bursts = false;          // block-level scan: bursts + tags go to h_bursts / h_tags, no packets are handed out
     bool keep_tags = false;            // AM_F_KEEP_TAGS: the packets' bursts + tags as well
     bool defer = false;                // enqueue only: AM_DEFERRED, completion is left to chain_collect
-    bool gate = false;                 // the address gate runs behind the slicing (scans that hand out packets, gate_mode != 0)
+    bool gate = false;                 // the address gate runs behind the slicing (scans that hand out packets, opt.gate_mode != 0)
     bool copy_tail = false;            // time shards: am_shard_keep_tail's copy goes between the slicing and the ticket
     bool has_entry = false;            // time shards: the start position is composed on the device from `entry`
     am_entry_src entry;
@@ -115,16 +116,16 @@ struct am_ctx {
     float thr_db = 0.0f;
     float thr_lin = 0.0f;
     int use_pmf = 0;
-    int fix_bits = 0;             // am_set_fix_errors: wrong bits a DF11 / DF17 reply may be repaired of (0: none, the reference's :179-182)
-    // am_set_long_formats: formats beyond the reference's four that are sliced as 112 bits (AM_LF_*).  The slicing
-    // kernels <FIX, GATE, 1> read them from scalars[AM_SW_LONG_FMT]; long_told is what that word holds (the block is zero when it
-    // is allocated), long_word the staging copy the host-to-device copy reads.
-    int long_mask = 0, long_told = 0;
+    // The opt-in decode options (am_options.h).  A context of its own is set through am_set_*; a context behind am_pipe / am_spipe
+    // gets the pipe's value, whole, when it is given a batch or a chunk.  Everything below that reads a setting reads it here.
+    am_decode_opts opt;
+    // am_set_long_formats: the slicing kernels <FIX, GATE, 1> read the enabled formats from scalars[AM_SW_LONG_FMT];
+    // long_told is what that word holds (the block is zero when it is allocated), long_word the staging copy the host-to-device
+    // copy reads.
+    int long_told = 0;
     uint32_t long_word = 0;
-    // am_set_address_gate (kernels: am_gate.inc).  Nothing below is allocated or launched while gate_mode is 0.
-    int gate_mode = 0;            // 0: off; 1: address/parity replies need a taught address; 2: and reserved formats are dropped
-    double gate_ttl_s = 60.0;     // how long a taught address lives, seconds
-    uint64_t gate_ttl = 1;        // ... in item counts: max(1, (uint64)(gate_ttl_s * rate)), formed when a scan is launched
+    // am_set_address_gate (kernels: am_gate.inc).  Nothing below is allocated or launched while opt.gate_mode is 0.
+    uint64_t gate_ttl = 1;        // the window in item counts: max(1, (uint64)(opt.gate_ttl_s * rate)), formed when a scan is launched
     DevBuf<am_gate_rec> gate_rec;                          // records of the scan
     DevBuf<unsigned long long> gate_scratch, gate_map;     // the call's table, the context's map
     DevBuf<unsigned long long> gate_multi;                 // K streams' offsets, then their emit limits (signed)
@@ -135,7 +136,6 @@ struct am_ctx {
     am_gate_args ga = {};         // ... and its arguments (am_k_gate_commit gets them again, with the count the host accepted)
     uint64_t gate_stat[3] = {0, 0, 0};   // taught, passed, dropped since am_create (accepted scans only)
     // am_set_address_repair: one wrong bit of an address/parity reply the gate fails, found among the addresses alive
-    int gate_repair = 0;          // 0: off; 1: on (inert while gate_mode is 0)
     DevBuf<uint32_t> gate_list;   // counters and the hit indices of the failed address/parity records (am_gate_args.rl)
     uint64_t repair_stat[2] = {0, 0};    // repaired, ambiguous since am_create (accepted scans only)
     // am_spipe_set_address_gate: the context slices a chunk of a pipe's stream.  The map is the pipe's RUNNING map,
@@ -345,14 +345,14 @@ int ensure_scalars(am_ctx *c)
 // the option on enqueues nothing here.
 int long_formats_tell(am_ctx *c)
 {
-    if (c->long_told == c->long_mask) return AM_OK;
+    if (c->long_told == c->opt.long_mask) return AM_OK;
     if (int rc = ensure_scalars(c); rc != AM_OK) return rc;
-    c->long_word = (uint32_t)c->long_mask << 18;
+    c->long_word = (uint32_t)c->opt.long_mask << 18;
     // (The source is pageable: the runtime copies so small a source into its own staging buffer before it returns, so the copy
     // is ordered on the stream but not asynchronous to the host.  Nothing relies on either: long_word is a member, not a local,
-    // and changes only here, after the setter -- which the pipes refuse while work is in flight -- changed long_mask.)
+    // and changes only here, after the setter -- which the pipes refuse while work is in flight -- changed opt.long_mask.)
     HIPCHK(c, hipMemcpyAsync(c->scalars.p + AM_SW_LONG_FMT, &c->long_word, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    c->long_told = c->long_mask;
+    c->long_told = c->opt.long_mask;
     return AM_OK;
 }
 
@@ -810,13 +810,13 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
     a.n_ptr = n_ptr;
     a.n = n_max;
     a.hist0 = (unsigned long long)c->geom.hist0;
-    c->gate_ttl = (uint64_t)(c->gate_ttl_s * c->rate);
+    c->gate_ttl = (uint64_t)(c->opt.gate_ttl_s * c->rate);
     if (c->gate_ttl < 1) c->gate_ttl = 1;
     a.ttl = c->gate_ttl;
-    a.mode = c->gate_mode;
+    a.mode = c->opt.gate_mode;
     gate_point_at(a, c->gate_pipe_map ? c->gate_pipe_map : c->gate_map.p);
     a.packets = packets;
-    if (c->gate_repair) {
+    if (c->opt.gate_repair) {
         ENSURE(c, c->gate_list, ((size_t)AM_GATE_RL_HDR + (n_max ? n_max : 1)) * sizeof(uint32_t));
         a.rl = c->gate_list.p;
         a.crc_pow = c->crc_pow.p;
@@ -840,8 +840,16 @@ int gate_prepare(am_ctx *c, uint32_t n_max, const uint32_t *n_ptr, am_packet *pa
     return AM_OK;
 }
 
-// Which GATE instantiation the slicing launch of a gated scan runs (gate_prepare has run: c->ga.rl says whether the repair is on)
-int slice_gate(const am_ctx *c, bool gate) { return gate ? (c->ga.rl ? 2 : 1) : 0; }
+// The option members of a slicing launch's am_slice_out -- which <FIX, GATE, LF> instantiation runs -- from the context's
+// settings, and the device word the LF kernels read (long_formats_tell).  Both sites that build an am_slice_out end with this.
+// gate: the scan runs the address gate, and gate_prepare has run: c->ga.rl says whether the repair is on.
+int slice_options(am_ctx *c, bool gate, am_slice_out &so)
+{
+    so.fix_bits = c->opt.fix_bits;
+    so.gate = gate ? (c->ga.rl ? 2 : 1) : 0;
+    so.long_mask = c->opt.long_mask;
+    return long_formats_tell(c);
+}
 
 // The host has accepted the scan whose records are resident and the stream goes on: its first n records' teaches enter the map.
 int gate_commit(am_ctx *c, uint32_t n)
@@ -994,8 +1002,7 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
     am_slice_out so;
     so.n_ptr = n_ptr; so.n_max = n_max; so.bursts_out = keep_dev ? c->bursts.p : nullptr; so.tags_out = keep_dev ? c->pin_tags : nullptr;
     so.crc_pow = c->crc_pow.p; so.packets = c->pin_packets; so.scalars = c->scalars.p; so.host_out = c->pin_scalars; so.Mp = Mp;
-    so.fix_bits = c->fix_bits; so.gate = slice_gate(c, gate); so.long_mask = c->long_mask;
-    if (int rc = long_formats_tell(c); rc != AM_OK) return rc;
+    if (int rc = slice_options(c, gate, so); rc != AM_OK) return rc;
     const am_stamp stamp = {base_abs, c->rate_i, c->tt_dev.p, (uint32_t)c->tt.size()};
     if (sc.sparse && !keep_bursts)
         // bb exists only around the candidates: the 240 soft chips of a hit are recomputed from the scan's samples
@@ -1174,7 +1181,7 @@ bool resolve_plan(const am_ctx *c, const am_shard_exit *msgs, uint32_t world, ui
     req.base_abs = c->shard_base;
     req.max_hits = (uint32_t)((c->shard_end - c->shard_start + (uint64_t)c->spc) / ((uint64_t)AM_BURST * (uint64_t)c->spc) + 2);
     req.copy_tail = c->keep_bytes != 0;
-    req.gate = c->gate_mode != 0;                              // (only a context of am_spipe gets here with the gate on)
+    req.gate = c->opt.gate_mode != 0;                              // (only a context of am_spipe gets here with the gate on)
     if (msgs) {
         req.has_entry = true;
         req.entry = shard_entry_src(c, msgs, world, rank, msg_cap);
@@ -1392,48 +1399,9 @@ double am_get_rate(const am_ctx *c) { return c ? c->rate : 0.0; }
 float am_get_threshold(const am_ctx *c) { return c ? c->thr_db : 0.0f; }
 int am_get_pmf(const am_ctx *c) { return c ? c->use_pmf : 0; }
 
-// slicer_impl.cc:179-182 drops every DF11 / DF17 reply with a bad syndrome; types.h:29-40 carries lowconfbits[] for a repair
-// that was never written.  The setting only selects which slicing kernels the next scan launches (am_slice_wave<FIX>).
-int am_set_fix_errors(am_ctx *c, int max_bits)
-{
-    if (!c) return AM_EINVAL;
-    if (max_bits < 0 || max_bits > 2) return fail(c, AM_EINVAL, "fix_errors: max_bits must be 0, 1 or 2");
-    c->fix_bits = max_bits;
-    return AM_OK;
-}
-int am_get_fix_errors(const am_ctx *c) { return c ? c->fix_bits : AM_EINVAL; }
+// (am_set_fix_errors, am_set_long_formats, am_set_address_gate, am_set_address_repair and their getters: with the pipes', at the
+// end of this file)
 
-// slicer_impl.cc:140 takes DF16/17/20/21 for long and cuts every other format to 56 bits, DF18 and DF19 among them.  The setting
-// selects the slicing kernels (am_slice_wave<FIX, GATE, LF>); the kernels read the enabled formats from the context's device block,
-// which the next slicing call writes on the context's stream in front of its launch (long_formats_tell).
-int am_set_long_formats(am_ctx *c, int mask)
-{
-    if (!c) return AM_EINVAL;
-    if (mask < 0 || mask > (AM_LF_DF18 | AM_LF_DF19)) return fail(c, AM_EINVAL, "long_formats: mask must be an OR of AM_LF_DF18 and AM_LF_DF19");
-    c->long_mask = mask;
-    return AM_OK;
-}
-int am_get_long_formats(const am_ctx *c) { return c ? c->long_mask : AM_EINVAL; }
-
-// slicer_impl.cc:170-182 checks parity for DF11 / DF17 only: in every other format the syndrome is "the address" and any bit
-// pattern passes.  The setting selects the slicing kernels (am_slice_wave<FIX, GATE>) and the gate launches behind them from the
-// next scan on; the map is kept (the window is formed from ttl and the rate when a scan is launched).
-int am_set_address_gate(am_ctx *c, int mode, double ttl_seconds)
-{
-    if (!c) return AM_EINVAL;
-    if (mode < 0 || mode > 2) return fail(c, AM_EINVAL, "address_gate: mode must be 0, 1 or 2");
-    if (!std::isfinite(ttl_seconds) || !(ttl_seconds > 0.0)) return fail(c, AM_EINVAL, "address_gate: ttl must be finite and positive");
-    c->gate_mode = mode;
-    c->gate_ttl_s = ttl_seconds;
-    return AM_OK;
-}
-int am_get_address_gate(const am_ctx *c, int *mode, double *ttl_seconds)
-{
-    if (!c) return AM_EINVAL;
-    if (mode) *mode = c->gate_mode;
-    if (ttl_seconds) *ttl_seconds = c->gate_ttl_s;
-    return AM_OK;
-}
 // taught / passed / dropped came with the tickets of the accepted scans; not_learned lives in front of the map and is fetched
 // when somebody asks (a wait for the context's stream, here and nowhere else)
 int am_get_address_gate_stats(const am_ctx *c, uint64_t *taught, uint64_t *passed, uint64_t *dropped, uint64_t *not_learned)
@@ -1454,16 +1422,6 @@ int am_get_address_gate_stats(const am_ctx *c, uint64_t *taught, uint64_t *passe
     return AM_OK;
 }
 
-// The gate drops "a real reply with one wrong bit", which reads as a reply of another aircraft; with this on, such a reply is
-// searched for the one bit whose flip gives it the address of an aircraft that is alive (am_k_gate_repair).  From the next scan on.
-int am_set_address_repair(am_ctx *c, int max_bits)
-{
-    if (!c) return AM_EINVAL;
-    if (max_bits < 0 || max_bits > 1) return fail(c, AM_EINVAL, "address_repair: max_bits must be 0 or 1");
-    c->gate_repair = max_bits;
-    return AM_OK;
-}
-int am_get_address_repair(const am_ctx *c) { return c ? c->gate_repair : AM_EINVAL; }
 int am_get_address_repair_stats(const am_ctx *c, uint64_t *repaired, uint64_t *ambiguous)
 {
     if (!c) return AM_EINVAL;
@@ -1594,7 +1552,7 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         req.max_hits = (uint32_t)((P1 - P0 + S) / ((uint64_t)AM_BURST * S) + 2);
         req.keep_tags = (flags & AM_F_KEEP_TAGS) != 0;
         req.defer = submit;
-        req.gate = c->gate_mode != 0;                       // these are the scans that hand out packets
+        req.gate = c->opt.gate_mode != 0;                       // these are the scans that hand out packets
         uint32_t fin = req.cur0;
         rc = run_chain_and_slice(c, req, &fin);
         c->ht[2] += am_now_us() - T2;
@@ -1828,12 +1786,15 @@ int am_collect(am_ctx *c, am_packet *out, uint64_t cap, uint64_t *n_out)
         uint32_t fin = P.req.cur0;
         int rc = chain_collect(c, P.req, P.n_max, &fin);
         if (rc == AM_RETRY_EXACT) {
-            // more candidates than the capacity the scan was launched for: redo it with the exact count, now
+            // more candidates than the capacity the scan was launched for: redo it with the exact count, now.  It slices with c->opt
+            // as it is NOW: behind am_pipe that is what the batch was submitted with (pipe_next; the pipe's setters are refused
+            // while a batch is in flight); a caller that changes a context of its own between am_submit_iq and am_collect --
+            // am_set_* does not refuse that, and never did -- gets the new setting here and the old one otherwise.
             rc = run_refine(c, c->scan);
             if (rc == AM_OK) {
                 TailReq req = P.req;
                 req.defer = false;
-                req.gate = c->gate_mode != 0;
+                req.gate = c->opt.gate_mode != 0;
                 rc = run_chain_and_slice(c, req, &fin);
             }
         }
@@ -2072,14 +2033,13 @@ int am_slicer_work(am_ctx *c, const float *bursts, const am_tag *tags, uint64_t 
     HIPCHK(c, hipMemcpyAsync(c->scalars.p + AM_SW_NBURSTS, &nb32, sizeof(nb32), hipMemcpyHostToDevice, c->stream));
     // the address gate on the block alone: the bursts are taken in the order given (item counts ascending, as the preamble block
     // emits them), nothing is ever repeated, so the call's teaches enter the map right behind its tests
-    const bool gate = c->gate_mode != 0;
+    const bool gate = c->opt.gate_mode != 0;
     if (gate)
         if (int rc = gate_prepare(c, nb32, nullptr, c->packets.p); rc != AM_OK) return rc;
     am_slice_out so;
     so.n_ptr = c->scalars.p + AM_SW_NBURSTS; so.n_max = nb32; so.bursts_out = nullptr; so.tags_out = nullptr;
     so.crc_pow = c->crc_pow.p; so.packets = c->packets.p; so.scalars = c->scalars.p; so.host_out = nullptr; so.Mp = nullptr;
-    so.fix_bits = c->fix_bits; so.gate = slice_gate(c, gate); so.long_mask = c->long_mask;
-    if (int rc = long_formats_tell(c); rc != AM_OK) return rc;
+    if (int rc = slice_options(c, gate, so); rc != AM_OK) return rc;
     HIPCHK(c, am_launch_slice(c->bursts.p, c->tags.p, so, c->stream));
     unsigned long long gcnt[3] = {0, 0, 0};
     uint32_t rcnt[2] = {0, 0};
@@ -2326,7 +2286,7 @@ static int shard_scan_core(am_ctx *c, const float *iq, uint64_t abs_start, uint6
 int am_shard_scan(am_ctx *c, const float *iq, uint64_t abs_start, uint64_t abs_end, uint64_t total_n,
                   uint32_t flags, am_shard_exit *table, uint64_t cap, uint64_t *n_table)
 {
-    if (c && c->gate_mode) {
+    if (c && c->opt.gate_mode) {
         if (n_table) *n_table = 0;
         return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     }
@@ -2346,7 +2306,7 @@ int am_shard_scan_async(am_ctx *c, const float *iq, uint64_t abs_start, uint64_t
                         uint32_t flags, am_shard_exit *msg_dev, uint64_t msg_cap)
 {
     if (!c || !msg_dev || msg_cap == 0) return AM_EINVAL;
-    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
+    if (c->opt.gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (!device_addressable(msg_dev)) return fail(c, AM_EINVAL, "am_shard_scan_async: msg_dev is not device-addressable memory");
     return shard_scan_core(c, iq, abs_start, abs_end, total_n, flags, nullptr, 0, nullptr, msg_dev, msg_cap);
 }
@@ -2451,7 +2411,7 @@ int am_shard_resolve(am_ctx *c, uint64_t cur_in, am_packet *out, uint64_t cap, u
 {
     if (!c) return AM_EINVAL;
     if (n_out) *n_out = 0;
-    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
+    if (c->opt.gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     return shard_resolve_sync(c, cur_in, out, cap, n_out);
 }
 
@@ -2461,7 +2421,7 @@ int am_shard_resolve_async(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t wo
     if (!c || !redo || (world && !msgs_dev) || rank >= world) return AM_EINVAL;
     if (n_out) *n_out = 0;
     *redo = 0;
-    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
+    if (c->opt.gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (!c->shard_ready) return fail(c, AM_EINVAL, "am_shard_scan_async has not been called");
     if (!device_addressable(msgs_dev)) return fail(c, AM_EINVAL, "am_shard_resolve_async: msgs_dev is not device-addressable memory");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2535,11 +2495,10 @@ struct am_spipe {
     int prev_slot = -1;
     uint64_t redone = 0;                // chunks that went through the synchronous path
     std::vector<am_shard_exit> host_tab;
+    am_decode_opts opt;                 // the stream's settings (am_spipe_set_*): copied into a slot's context with every chunk (spipe_enqueue)
     // am_spipe_set_address_gate / _repair: one stream, one map -- kept twice.  The RUNNING map is what the chunks in
     // flight read and teach, in stream order (an event from chunk to chunk); the ACCEPTED map is taught only by chunks the host has
     // collected, and is what the running map is put back to when a chunk is redone.  Nothing is allocated while the gate is off.
-    int gate_mode = 0, gate_repair = 0;
-    double gate_ttl_s = 60.0;
     unsigned long long *gate_running = nullptr, *gate_accepted = nullptr;
     bool gate_dirty = false;            // a gated chunk has been enqueued since the maps were last emptied
     uint64_t gate_stat[3] = {0, 0, 0}, repair_stat[2] = {0, 0};   // of the chunks collected (never of a discarded attempt)
@@ -2701,10 +2660,10 @@ static int spipe_enqueue(am_spipe *p, size_t k)
     uint64_t a0, a1, total;
     const float *ptr;
     spipe_bounds(p, sl, &a0, &a1, &total, &ptr);
-    c->gate_mode = p->gate_mode; c->gate_ttl_s = p->gate_ttl_s; c->gate_repair = p->gate_repair;
+    c->opt = p->opt;                    // the one point where a setting of the pipe reaches a context
     c->gate_wait = nullptr;
     c->gate_done = nullptr;
-    if (p->gate_mode) {
+    if (p->opt.gate_mode) {
         if (int rcg = spipe_gate_ensure(p, c); rcg != AM_OK) return rcg;
         c->gate_pipe_map = p->gate_running;
         c->gate_done = sl.gate_done;
@@ -2729,7 +2688,7 @@ static int spipe_enqueue(am_spipe *p, size_t k)
         HIPCHK(c, hipStreamWaitEvent(c->stream, pv.done, 0));
     }
     rc = shard_resolve_enqueue(c, sl.msg, 1, 0, p->msg_cap, cur_in, nullptr, sl.done);
-    if (rc != AM_OK || !p->gate_mode) return rc;
+    if (rc != AM_OK || !p->opt.gate_mode) return rc;
     return spipe_gate_pass_on(c);
 }
 
@@ -2810,47 +2769,6 @@ int am_spipe_set_rx_time(am_spipe *p, uint64_t offset, uint64_t secs, double fra
     return AM_OK;
 }
 
-// (a chunk that has to be redone is sliced again when it is collected: the setting may not change under the chunks in flight)
-int am_spipe_set_fix_errors(am_spipe *p, int max_bits)
-{
-    if (!p) return AM_EINVAL;
-    if (max_bits < 0 || max_bits > 2) return spipe_fail(p, AM_EINVAL, "fix_errors: max_bits must be 0, 1 or 2");
-    if (p->inflight) return spipe_fail(p, AM_EINVAL, "fix_errors: collect the chunks in flight first");
-    for (am_spipe_slot &sl : p->slot) sl.c->fix_bits = max_bits;
-    return AM_OK;
-}
-int am_spipe_get_fix_errors(const am_spipe *p) { return p && !p->slot.empty() ? p->slot[0].c->fix_bits : AM_EINVAL; }
-
-// (likewise; every context behind the pipe writes its own device word in front of its next slicing launch)
-int am_spipe_set_long_formats(am_spipe *p, int mask)
-{
-    if (!p) return AM_EINVAL;
-    if (mask < 0 || mask > (AM_LF_DF18 | AM_LF_DF19)) return spipe_fail(p, AM_EINVAL, "long_formats: mask must be an OR of AM_LF_DF18 and AM_LF_DF19");
-    if (p->inflight) return spipe_fail(p, AM_EINVAL, "long_formats: collect the chunks in flight first");
-    for (am_spipe_slot &sl : p->slot) sl.c->long_mask = mask;
-    return AM_OK;
-}
-int am_spipe_get_long_formats(const am_spipe *p) { return p && !p->slot.empty() ? p->slot[0].c->long_mask : AM_EINVAL; }
-
-// The address gate for the pipe's one stream.  The setting is the pipe's and goes to a context with every chunk; the
-// maps are kept across a new setting, as am_set_address_gate keeps the context's.
-int am_spipe_set_address_gate(am_spipe *p, int mode, double ttl_seconds)
-{
-    if (!p) return AM_EINVAL;
-    if (mode < 0 || mode > 2) return spipe_fail(p, AM_EINVAL, "address_gate: mode must be 0, 1 or 2");
-    if (!std::isfinite(ttl_seconds) || !(ttl_seconds > 0.0)) return spipe_fail(p, AM_EINVAL, "address_gate: ttl must be finite and positive");
-    if (p->inflight) return spipe_fail(p, AM_EINVAL, "address_gate: collect the chunks in flight first");
-    p->gate_mode = mode;
-    p->gate_ttl_s = ttl_seconds;
-    return AM_OK;
-}
-int am_spipe_get_address_gate(const am_spipe *p, int *mode, double *ttl_seconds)
-{
-    if (!p) return AM_EINVAL;
-    if (mode) *mode = p->gate_mode;
-    if (ttl_seconds) *ttl_seconds = p->gate_ttl_s;
-    return AM_OK;
-}
 // (not_learned is counted where the accepted map is taught; fetched when somebody asks, behind every stream of the pipe)
 int am_spipe_get_address_gate_stats(const am_spipe *p, uint64_t *taught, uint64_t *passed, uint64_t *dropped, uint64_t *not_learned)
 {
@@ -2870,15 +2788,6 @@ int am_spipe_get_address_gate_stats(const am_spipe *p, uint64_t *taught, uint64_
     }
     return AM_OK;
 }
-int am_spipe_set_address_repair(am_spipe *p, int max_bits)
-{
-    if (!p) return AM_EINVAL;
-    if (max_bits < 0 || max_bits > 1) return spipe_fail(p, AM_EINVAL, "address_repair: max_bits must be 0 or 1");
-    if (p->inflight) return spipe_fail(p, AM_EINVAL, "address_repair: collect the chunks in flight first");
-    p->gate_repair = max_bits;
-    return AM_OK;
-}
-int am_spipe_get_address_repair(const am_spipe *p) { return p ? p->gate_repair : AM_EINVAL; }
 int am_spipe_get_address_repair_stats(const am_spipe *p, uint64_t *repaired, uint64_t *ambiguous)
 {
     if (!p) return AM_EINVAL;
@@ -2925,7 +2834,9 @@ int am_spipe_collect(am_spipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
         if (rc != AM_OK) { p->last_fail = c; return rc; }
         if (redo) {
             // the chunks behind this one composed their entry from a word that was never written: drain them, redo this chunk with
-            // the tables on the host, submit them again
+            // the tables on the host, submit them again.  (Settings: this chunk is scanned again with the c->opt it got when it was
+            // enqueued, the chunks behind it get p->opt once more from spipe_enqueue -- the same value, since every am_spipe_set_*
+            // has been refused from the first of these submits on.)
             p->redone++;
             const size_t D = p->slot.size();
             for (size_t j = 1; j < p->inflight; j++) {
@@ -2937,7 +2848,7 @@ int am_spipe_collect(am_spipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
                 if (rc != AM_OK) { p->last_fail = cj; return rc; }
             }
             p->last_fail = c;                                   // (should a HIP call below fail: the message is this context's)
-            if (p->gate_mode) {
+            if (p->opt.gate_mode) {
                 // what this attempt and the chunks behind it taught the running map never happened: it becomes the accepted map
                 // again, which holds the chunks collected so far and nothing else (their commits may still be running on streams
                 // nothing was enqueued on since)
@@ -2958,7 +2869,7 @@ int am_spipe_collect(am_spipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
             uint64_t got = 0;
             rc = shard_resolve_sync(c, entry, nullptr, 0, &got);   // (the packets stay in the context's hand-out list: AM_ECAPACITY is expected)
             if (rc != AM_OK && rc != AM_ECAPACITY) { p->last_fail = c; return rc; }
-            if (p->gate_mode)                                   // (what the chunks submitted again wait for)
+            if (p->opt.gate_mode)                               // (what the chunks submitted again wait for)
                 if (int grc = spipe_gate_pass_on(c); grc != AM_OK) return grc;
             rc = am_shard_set_exit(c, leave);
             if (rc != AM_OK) { p->last_fail = c; return rc; }
@@ -2976,7 +2887,7 @@ int am_spipe_collect(am_spipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
             p->prev_iq = piq; p->prev_n = pn; p->prev_slot = pslot;
         }
         p->exit_host = leave;
-        if (p->gate_mode)
+        if (p->opt.gate_mode)
             if (int grc = spipe_gate_accept(p, k, gate_before); grc != AM_OK) { p->last_fail = c; return grc; }
     }
     const int hrc = hand_out(c, out, cap, n_out);
@@ -3009,7 +2920,7 @@ int am_shard_resolve_submit(am_ctx *c, const am_shard_exit *msgs_dev, uint32_t w
                             const uint64_t *cur_in_dev, uint64_t *carry_out_dev)
 {
     if (!c || (world && !msgs_dev) || rank >= world) return AM_EINVAL;
-    if (c->gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
+    if (c->opt.gate_mode) return fail(c, AM_ENOTSUP, "time shards: not with the address gate (its map would have to cross ranks)");
     if (!c->shard_ready) return fail(c, AM_EINVAL, "am_shard_scan_async has not been called");
     if (c->pend.active) return fail(c, AM_EINVAL, "a submitted resolve step has not been collected (am_shard_resolve_collect)");
     if (!device_addressable(msgs_dev) || (cur_in_dev && !device_addressable(cur_in_dev)) || (carry_out_dev && !device_addressable(carry_out_dev)))
@@ -3051,9 +2962,27 @@ extern "C" {
 struct am_pipe {
     std::vector<am_ctx *> sub;
     size_t head = 0, inflight = 0;
+    am_decode_opts opt;                  // the pipe's settings (am_pipe_set_*): copied into a context with every batch it is given
     const am_ctx *last_fail = nullptr;   // the sub-context whose call failed last (am_pipe_last_error)
     char err[128] = "";                  // ... or the pipe's own message
 };
+
+static int pipe_fail(am_pipe *p, int code, const char *what)
+{
+    p->last_fail = nullptr;
+    snprintf(p->err, sizeof(p->err), "%s", what);
+    return code;
+}
+
+// The context that takes the pipe's next batch, with the pipe's settings: the one point where they reach a context.  (A batch
+// that am_collect scans or slices again does so with what it was submitted with: nothing changes a context's value but this, and
+// the setters are refused while a batch is in flight.)
+static am_ctx *pipe_next(am_pipe *p)
+{
+    am_ctx *c = p->sub[(p->head + p->inflight) % p->sub.size()];
+    c->opt = p->opt;
+    return c;
+}
 
 am_pipe *am_pipe_create(int device, double rate, float threshold_db, int use_pmf, int use_dcblock, int depth, int *err)
 {
@@ -3101,80 +3030,11 @@ void am_pipe_destroy(am_pipe *p)
 int am_pipe_depth(const am_pipe *p) { return p ? (int)p->sub.size() : AM_EINVAL; }
 int am_pipe_in_flight(const am_pipe *p) { return p ? (int)p->inflight : AM_EINVAL; }
 
-// (a batch whose scan met more candidates than it was launched for is scanned and sliced again when it is collected: the
-// setting may not change under the batches in flight)
-int am_pipe_set_fix_errors(am_pipe *p, int max_bits)
-{
-    if (!p) return AM_EINVAL;
-    if (max_bits < 0 || max_bits > 2 || p->inflight) {
-        p->last_fail = nullptr;
-        snprintf(p->err, sizeof(p->err), "%s", p->inflight ? "fix_errors: collect the batches in flight first"
-                                                           : "fix_errors: max_bits must be 0, 1 or 2");
-        return AM_EINVAL;
-    }
-    for (am_ctx *c : p->sub) c->fix_bits = max_bits;
-    return AM_OK;
-}
-int am_pipe_get_fix_errors(const am_pipe *p) { return p && !p->sub.empty() ? p->sub[0]->fix_bits : AM_EINVAL; }
-
-// (likewise; every context behind the pipe writes its own device word in front of its next slicing launch)
-int am_pipe_set_long_formats(am_pipe *p, int mask)
-{
-    if (!p) return AM_EINVAL;
-    if (mask < 0 || mask > (AM_LF_DF18 | AM_LF_DF19) || p->inflight) {
-        p->last_fail = nullptr;
-        snprintf(p->err, sizeof(p->err), "%s", p->inflight ? "long_formats: collect the batches in flight first"
-                                                           : "long_formats: mask must be an OR of AM_LF_DF18 and AM_LF_DF19");
-        return AM_EINVAL;
-    }
-    for (am_ctx *c : p->sub) c->long_mask = mask;
-    return AM_OK;
-}
-int am_pipe_get_long_formats(const am_pipe *p) { return p && !p->sub.empty() ? p->sub[0]->long_mask : AM_EINVAL; }
-
-// (every batch is a whole stream: the map of the context that takes it is empty when it starts and is emptied when it ends)
-int am_pipe_set_address_gate(am_pipe *p, int mode, double ttl_seconds)
-{
-    if (!p) return AM_EINVAL;
-    const bool bad = mode < 0 || mode > 2 || !std::isfinite(ttl_seconds) || !(ttl_seconds > 0.0);
-    if (bad || p->inflight) {
-        p->last_fail = nullptr;
-        snprintf(p->err, sizeof(p->err), "%s", bad ? "address_gate: mode must be 0, 1 or 2 and ttl finite and positive"
-                                                   : "address_gate: collect the batches in flight first");
-        return AM_EINVAL;
-    }
-    for (am_ctx *c : p->sub) { c->gate_mode = mode; c->gate_ttl_s = ttl_seconds; }
-    return AM_OK;
-}
-int am_pipe_get_address_gate(const am_pipe *p, int *mode, double *ttl_seconds)
-{
-    if (!p || p->sub.empty()) return AM_EINVAL;
-    return am_get_address_gate(p->sub[0], mode, ttl_seconds);
-}
-
-int am_pipe_set_address_repair(am_pipe *p, int max_bits)
-{
-    if (!p) return AM_EINVAL;
-    if (max_bits < 0 || max_bits > 1 || p->inflight) {
-        p->last_fail = nullptr;
-        snprintf(p->err, sizeof(p->err), "%s", p->inflight ? "address_repair: collect the batches in flight first"
-                                                           : "address_repair: max_bits must be 0 or 1");
-        return AM_EINVAL;
-    }
-    for (am_ctx *c : p->sub) c->gate_repair = max_bits;
-    return AM_OK;
-}
-int am_pipe_get_address_repair(const am_pipe *p) { return p && !p->sub.empty() ? p->sub[0]->gate_repair : AM_EINVAL; }
-
 int am_pipe_submit(am_pipe *p, const float *iq, uint64_t n, uint32_t flags)
 {
     if (!p) return AM_EINVAL;
-    if (p->inflight == p->sub.size()) {
-        p->last_fail = nullptr;
-        snprintf(p->err, sizeof(p->err), "every context of the pipe has a batch in flight: collect the oldest one first");
-        return AM_ECAPACITY;
-    }
-    am_ctx *c = p->sub[(p->head + p->inflight) % p->sub.size()];
+    if (p->inflight == p->sub.size()) return pipe_fail(p, AM_ECAPACITY, "every context of the pipe has a batch in flight: collect the oldest one first");
+    am_ctx *c = pipe_next(p);
     const int rc = am_submit_iq(c, iq, n, flags | AM_F_FLUSH);
     if (rc == AM_OK) p->inflight++;
     else p->last_fail = c;
@@ -3186,12 +3046,8 @@ int am_pipe_submit(am_pipe *p, const float *iq, uint64_t n, uint32_t flags)
 int am_pipe_submit_multi(am_pipe *p, float *iq, uint32_t k, const uint64_t *n, uint32_t flags)
 {
     if (!p) return AM_EINVAL;
-    if (p->inflight == p->sub.size()) {
-        p->last_fail = nullptr;
-        snprintf(p->err, sizeof(p->err), "every context of the pipe has a batch in flight: collect the oldest one first");
-        return AM_ECAPACITY;
-    }
-    am_ctx *c = p->sub[(p->head + p->inflight) % p->sub.size()];
+    if (p->inflight == p->sub.size()) return pipe_fail(p, AM_ECAPACITY, "every context of the pipe has a batch in flight: collect the oldest one first");
+    am_ctx *c = pipe_next(p);
     const int rc = am_submit_multi(c, iq, k, n, flags);
     if (rc == AM_OK) p->inflight++;
     else p->last_fail = c;
@@ -3211,11 +3067,7 @@ int am_pipe_collect(am_pipe *p, am_packet *out, uint64_t cap, uint64_t *n_out)
 {
     if (!p) return AM_EINVAL;
     if (n_out) *n_out = 0;
-    if (p->inflight == 0) {
-        p->last_fail = nullptr;
-        snprintf(p->err, sizeof(p->err), "no batch in flight");
-        return AM_EINVAL;
-    }
+    if (p->inflight == 0) return pipe_fail(p, AM_EINVAL, "no batch in flight");
     am_ctx *c = p->sub[p->head];
     const int rc = am_collect(c, out, cap, n_out);
     if (rc != AM_OK) p->last_fail = c;
@@ -3262,5 +3114,90 @@ long long am_last_num_candidates(const am_ctx *c)
 {
     return c ? (long long)c->last_M : (long long)AM_EINVAL;
 }
+
+} // extern "C"
+
+/* ---- the opt-in decode options: one value per handle (am_options.h), one way to set it ------------------------------------
+ * am_set_fix_errors      slicer_impl.cc:179-182 drops every DF11 / DF17 reply with a bad syndrome; types.h:29-40 carries
+ *                        lowconfbits[] for a repair that was never written.  Selects the slicing kernels (am_slice_wave<FIX>).
+ * am_set_long_formats    slicer_impl.cc:140 takes DF16/17/20/21 for long and cuts every other format to 56 bits, DF18 and DF19
+ *                        among them.  Selects the slicing kernels (<FIX, GATE, LF>), which read the enabled formats from the
+ *                        context's device block (long_formats_tell).
+ * am_set_address_gate    slicer_impl.cc:170-182 checks parity for DF11 / DF17 only: in every other format the syndrome is "the
+ *                        address" and any bit pattern passes.  Selects the slicing kernels (<FIX, GATE>) and the gate launches
+ *                        behind them; the map is kept (the window is formed from ttl and the rate when a scan is launched).
+ * am_set_address_repair  the gate drops "a real reply with one wrong bit", which reads as a reply of another aircraft; with
+ *                        this on, such a reply is searched for the one bit whose flip gives it the address of an aircraft that
+ *                        is alive (am_k_gate_repair).
+ * A setting takes effect with the next scan.  A context of its own reads its value where it slices (slice_options,
+ * gate_prepare).  A pipe's value is the pipe's: am_pipe copies it into the context that takes a batch (pipe_next: every batch is
+ * a whole stream, its map is the context's own and empty), am_spipe into the context that takes a chunk (spipe_enqueue: the map
+ * is the pipe's, kept across a new setting).  Both refuse a new setting while work is in flight, because a batch or a chunk may be
+ * scanned and sliced again when it is collected (am_collect's redo with the exact count; am_spipe_collect's synchronous redo,
+ * which submits the chunks behind it again through spipe_enqueue): what is in flight ends with the setting it started with. */
+namespace {
+
+int opt_fail(am_ctx *c, const char *what) { return fail(c, AM_EINVAL, what); }
+int opt_fail(am_pipe *p, const char *what) { return pipe_fail(p, AM_EINVAL, what); }
+int opt_fail(am_spipe *p, const char *what) { return spipe_fail(p, AM_EINVAL, what); }
+// what the handle has in flight, by name; null: nothing, the setting may change
+const char *opt_busy(const am_ctx *) { return nullptr; }
+const char *opt_busy(const am_pipe *p) { return p->inflight ? "batches" : nullptr; }
+const char *opt_busy(const am_spipe *p) { return p->inflight ? "chunks" : nullptr; }
+
+// name: the option, as its messages begin; apply: its function of am_options.h
+template <class H, class... A>
+int set_option(H *h, const char *name, const char *(*apply)(am_decode_opts &, A...), A... value)
+{
+    if (!h) return AM_EINVAL;
+    am_decode_opts o = h->opt;
+    if (const char *msg = apply(o, value...)) return opt_fail(h, msg);
+    if (const char *what = opt_busy(h)) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "%s: collect the %s in flight first", name, what);
+        return opt_fail(h, msg);
+    }
+    h->opt = o;
+    return AM_OK;
+}
+
+template <class H>
+int get_address_gate(const H *h, int *mode, double *ttl_seconds)
+{
+    if (!h) return AM_EINVAL;
+    if (mode) *mode = h->opt.gate_mode;
+    if (ttl_seconds) *ttl_seconds = h->opt.gate_ttl_s;
+    return AM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int am_set_fix_errors(am_ctx *c, int max_bits) { return set_option(c, "fix_errors", am_opt_fix_errors, max_bits); }
+int am_pipe_set_fix_errors(am_pipe *p, int max_bits) { return set_option(p, "fix_errors", am_opt_fix_errors, max_bits); }
+int am_spipe_set_fix_errors(am_spipe *p, int max_bits) { return set_option(p, "fix_errors", am_opt_fix_errors, max_bits); }
+int am_set_long_formats(am_ctx *c, int mask) { return set_option(c, "long_formats", am_opt_long_formats, mask); }
+int am_pipe_set_long_formats(am_pipe *p, int mask) { return set_option(p, "long_formats", am_opt_long_formats, mask); }
+int am_spipe_set_long_formats(am_spipe *p, int mask) { return set_option(p, "long_formats", am_opt_long_formats, mask); }
+int am_set_address_gate(am_ctx *c, int mode, double ttl_seconds) { return set_option(c, "address_gate", am_opt_address_gate, mode, ttl_seconds); }
+int am_pipe_set_address_gate(am_pipe *p, int mode, double ttl_seconds) { return set_option(p, "address_gate", am_opt_address_gate, mode, ttl_seconds); }
+int am_spipe_set_address_gate(am_spipe *p, int mode, double ttl_seconds) { return set_option(p, "address_gate", am_opt_address_gate, mode, ttl_seconds); }
+int am_set_address_repair(am_ctx *c, int max_bits) { return set_option(c, "address_repair", am_opt_address_repair, max_bits); }
+int am_pipe_set_address_repair(am_pipe *p, int max_bits) { return set_option(p, "address_repair", am_opt_address_repair, max_bits); }
+int am_spipe_set_address_repair(am_spipe *p, int max_bits) { return set_option(p, "address_repair", am_opt_address_repair, max_bits); }
+
+int am_get_fix_errors(const am_ctx *c) { return c ? c->opt.fix_bits : AM_EINVAL; }
+int am_pipe_get_fix_errors(const am_pipe *p) { return p ? p->opt.fix_bits : AM_EINVAL; }
+int am_spipe_get_fix_errors(const am_spipe *p) { return p ? p->opt.fix_bits : AM_EINVAL; }
+int am_get_long_formats(const am_ctx *c) { return c ? c->opt.long_mask : AM_EINVAL; }
+int am_pipe_get_long_formats(const am_pipe *p) { return p ? p->opt.long_mask : AM_EINVAL; }
+int am_spipe_get_long_formats(const am_spipe *p) { return p ? p->opt.long_mask : AM_EINVAL; }
+int am_get_address_gate(const am_ctx *c, int *mode, double *ttl_seconds) { return get_address_gate(c, mode, ttl_seconds); }
+int am_pipe_get_address_gate(const am_pipe *p, int *mode, double *ttl_seconds) { return get_address_gate(p, mode, ttl_seconds); }
+int am_spipe_get_address_gate(const am_spipe *p, int *mode, double *ttl_seconds) { return get_address_gate(p, mode, ttl_seconds); }
+int am_get_address_repair(const am_ctx *c) { return c ? c->opt.gate_repair : AM_EINVAL; }
+int am_pipe_get_address_repair(const am_pipe *p) { return p ? p->opt.gate_repair : AM_EINVAL; }
+int am_spipe_get_address_repair(const am_spipe *p) { return p ? p->opt.gate_repair : AM_EINVAL; }
 
 } // extern "C"

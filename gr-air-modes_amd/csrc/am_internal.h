@@ -377,8 +377,9 @@ struct am_time_tag {
  * scalars[AM_SW_LONG_FMT] (the host has written them there on the same stream); 0 = the kernels as they are without the option.
  * NO MEMBER HAS AN INITIALISER, and no site value-initialises one of these ("am_slice_out o = {};"): a silent 0 in fix_bits,
  * gate or long_mask would run a scan without the option and nobody would notice.  Each of the two sites that build one
- * (chain_finish, am_slicer_work) assigns all twelve members by name, in this order, so that a missing one shows when the site is
- * read. */
+ * (chain_finish, am_slicer_work) assigns the first nine members by name, in this order, so that a missing one shows when the
+ * site is read; the last three -- fix_bits, gate, long_mask -- are assigned by slice_options (am_capi.hip), from the context's
+ * am_decode_opts, at both sites. */
 struct am_slice_out {
     const uint32_t *n_ptr;     /* device-side number of hits                                                     */
     uint32_t n_max;            /* upper bound used for the grid                                                  */

@@ -179,6 +179,12 @@ class Library(object):
         L.am_fetch_candidates.argtypes = [vp, vp, vp, vp, vp, u64, pu64]
         L.am_last_frontend.restype = C.c_int
         L.am_last_frontend.argtypes = [vp]
+        L.am_set_raw_front_end.restype = C.c_int
+        L.am_set_raw_front_end.argtypes = [vp, ci]
+        L.am_get_raw_front_end.restype = C.c_int
+        L.am_get_raw_front_end.argtypes = [vp]
+        L.am_last_scan_format.restype = C.c_int
+        L.am_last_scan_format.argtypes = [vp]
         L.am_sample_bytes.restype = C.c_size_t
         L.am_sample_bytes.argtypes = [ci]
         L.am_unpack.argtypes = [vp, vp, u64, ci, u32, vp]
@@ -451,6 +457,18 @@ class Context(_DecodeOptions, _DecodeStats):
     def last_frontend(self):
         """3 = streaming kernel, 2 = tile kernel, 1 = rate-generic kernels, 0 = no scan yet (diagnostic)."""
         return int(self.lib.L.am_last_frontend(self._h))
+
+    def set_raw_front_end(self, on):
+        """Diagnostic switch (default on): at 64 Msps a raw stream is scanned as it is, without the float copy.  Takes effect
+        when the next stream starts."""
+        self._chk(self.lib.L.am_set_raw_front_end(self._h, 1 if on else 0))
+
+    def get_raw_front_end(self):
+        return bool(self.lib.L.am_get_raw_front_end(self._h))
+
+    def last_scan_format(self):
+        """formats.code of what the last scan's front end read: that of the input on the raw route, else 0 (float32)."""
+        return int(self.lib.L.am_last_scan_format(self._h))
 
     def last_timing(self):
         """(whole call, dominant kernel) device milliseconds of the last call."""

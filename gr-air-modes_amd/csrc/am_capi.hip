@@ -71,7 +71,8 @@ struct Scan {
     const uint32_t *Mp = nullptr;      // ... with the count on the device (speculative launch); null: M is exact
     bool jump_ready = false;           // the refinement already wrote the chain's successor array (am_k_cand / am_k_refine_*)
     bool sparse = false;               // bb (ref.bb) exists only around candidates (streaming front end): burst extraction
-    const float *src = nullptr;        // ... recomputes from these samples, which must stay valid until the scan's hits are sliced
+    const void *src = nullptr;         // ... recomputes from these samples, which must stay valid until the scan's hits are sliced
+    int fmt = AM_FMT_CF32;             // ... and which are of this format: what the scan's kernels read (am_last_scan_format)
     uint64_t src_abs0 = 0, src_abs1 = 0;
     am_fe_layout fe;                   // streaming front end: the bitmap it left (am_fe_plan, through the launcher)
     am_rows_args rows = {};            // ... and what forms the bb rows around candidates (64 Msps: from IQ, behind the front end)
@@ -153,6 +154,10 @@ struct am_ctx {
     double spec_density = 0.0;    // candidates per position, previous scan
     double spec_floor = 16384.0;  // slack added to the extrapolated capacity (AIRMODES_SPEC_FLOOR, tests)
     int use_dcblock = 0;          // a2: dc_blocker_cc(100*spc, False) in front of |.|^2 (rx_path.py:39-41)
+    // am_set_raw_front_end: a raw stream at 64 Msps is scanned as it is -- am_k_fe3<FMT> and what follows it read the
+    // integers, the carried tail stays at raw width, am_k_unpack does not run.  The A/B lever of tests and measurement.
+    int raw_fe = 1;               // the switch: read when a stream starts
+    int view_fmt = AM_FMT_CF32;   // the format of this stream's device view and carried tail: the input's on the native route, else float32
     const float *zt_base[2] = {nullptr, nullptr};   // where the zero tail of bb / avg was last written
     uint64_t zt_n[2] = {0, 0};
     // host-side wall-clock trace (AIRMODES_HOST_TRACE): cumulative microseconds per section
@@ -212,7 +217,7 @@ struct am_ctx {
     uint64_t chain_cur = 0;   // position at which the greedy scan resumes
     uint64_t carry_abs0 = 0;
     uint64_t carry_n = 0;
-    DevBuf<float> carry, carry2;
+    DevBuf<float> carry, carry2;  // (view_fmt other than AM_FMT_CF32: carry_n samples of that format, no floats; c->src likewise)
 
     // work buffers (grow only)
     DevBuf<unsigned char> raw_in; // raw bytes of a host chunk in a native sample format (am_process_samples, am_unpack)
@@ -547,6 +552,10 @@ int run_frontend(am_ctx *c, const float *src, uint64_t src_abs0, uint64_t src_ab
     return AM_OK;
 }
 
+// A raw stream can be scanned as it is where the scan runs am_k_fe3 and am_k_refine_seg (64 Msps, product configuration) on the
+// samples themselves: no DC blocker in front.  (The row loader of am_k_gather_wg -- fused_refine off, test builds -- reads float32.)
+static bool native_front_end(const am_ctx *c);
+
 // Which kernels a scan of this context runs.  PATH_TILE exists in TEST builds only (-DAM_WITH_TILE_KERNEL: tests/gpu_variants,
 // tests/emu; round 5: the product library no longer carries am_k_fe2 nor the split refinement behind it).
 // dense_wanted: the caller wants bb / avg as whole arrays (block-level am_frontend_work).
@@ -558,6 +567,11 @@ static ScanPath scan_path(const am_ctx *c, bool dense_wanted)
     if (am_fe2_tile(c->spc)) return PATH_TILE;
 #endif
     return PATH_GENERIC;
+}
+
+static bool native_front_end(const am_ctx *c)
+{
+    return scan_path(c, false) == PATH_STREAM && am_fe4_uses_fe3(c->spc) && c->fused_refine && !c->use_dcblock;
 }
 
 // A scan starts: whatever the one before left for its tail is gone (which front end ran last stays on record until one runs again)
@@ -683,10 +697,15 @@ int run_candidates(am_ctx *c, const float *bb, const float *avg, uint32_t j0, ui
 
 // IQ -> bb, avg and the refined candidate records for positions [j0, j1): the fused
 // specialisation when this samples-per-chip has one, the generic kernel pair otherwise.  The result is the context's resident scan.
-int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uint64_t src_abs1, uint64_t out_abs0,
-                             uint64_t out_n, float *bb, float *avg, uint32_t j0, uint32_t j1, bool may_speculate = false)
+// fmt: the format of the samples at vsrc; other than AM_FMT_CF32 only where native_front_end() says so.
+int run_front_and_candidates(am_ctx *c, const void *vsrc, uint64_t src_abs0, uint64_t src_abs1, uint64_t out_abs0,
+                             uint64_t out_n, float *bb, float *avg, uint32_t j0, uint32_t j1, bool may_speculate = false,
+                             int fmt = AM_FMT_CF32)
 {
     const ScanPath path = scan_path(c, avg != nullptr);
+    if (fmt != AM_FMT_CF32 && !(path == PATH_STREAM && native_front_end(c)))
+        return fail(c, AM_EINVAL, "internal: no kernel reads raw samples on this path");
+    const float *src = static_cast<const float *>(vsrc);      // (what the float32-only kernels below are handed)
     HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
     if (path == PATH_GENERIC) {
         if (!avg) return fail(c, AM_EINVAL, "internal: the rate-generic kernels need the dense reference-level array");
@@ -699,7 +718,7 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
         return rc;
     }
     Scan &sc = new_scan(c);
-    sc.path = path; sc.src = src; sc.src_abs0 = src_abs0; sc.src_abs1 = src_abs1;
+    sc.path = path; sc.src = vsrc; sc.fmt = fmt; sc.src_abs0 = src_abs0; sc.src_abs1 = src_abs1;
     const uint32_t end_j = (uint32_t)std::min<uint64_t>(src_abs1 > out_abs0 ? src_abs1 - out_abs0 : 0, 0xFFFFFFFFull);
     if (path == PATH_STREAM) {
         // streaming kernel: candidate bitmap + per-workgroup counts; bb and the reference level only around candidates
@@ -718,7 +737,7 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
         // the front end, not written by it (~42 MB of stores per 64 M samples that the dominant kernel does not make) -- by
         // am_k_refine_seg, which can place segments of two lengths, or (test builds) by am_k_gather_wg
         const RefineKind kind = !(sizes.wbits == 32 && sizes.lag == 288) ? REFINE_LATE : c->fused_refine ? REFINE_SEG : REFINE_LATE_ROWS;
-        sc.rows = {rows_from_iq(kind) ? src : nullptr, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0, (long long)out_n,
+        sc.rows = {rows_from_iq(kind) ? vsrc : nullptr, fmt, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0, (long long)out_n,
                    bb, nullptr, c->use_pmf, c->s1};
         if (kind == REFINE_LATE_ROWS) {
             // one float per array chip: the largest bb of every row formed (am_k_refine_late: whole chips of a quiet zone)
@@ -726,7 +745,7 @@ int run_front_and_candidates(am_ctx *c, const float *src, uint64_t src_abs0, uin
             sc.rows.bb_max = c->bbmax.p;
             if (c->poison) HIPCHK(c, hipMemsetAsync(c->bbmax.p, 0xFF, ((size_t)(out_n / 32) + 64) * sizeof(float), c->stream));
         }
-        const am_fe_stream_req r = {src, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0, (long long)out_n,
+        const am_fe_stream_req r = {vsrc, fmt, (long long)src_abs0, (long long)src_abs1, (long long)out_abs0, (long long)out_n,
                                     rows_from_iq(kind) ? nullptr : bb, c->avg.p, j0, j1, c->use_pmf, c->s1, c->sL, c->thr_lin,
                                     c->bits.p, c->blk_cnt.p, c->wgmax.p};
         HIPCHK(c, am_launch_fe4(c->spc, r, &sc.fe, c->stream, c->fe_wgs_per_cu, kind == REFINE_SEG));
@@ -1006,7 +1025,7 @@ int chain_finish(am_ctx *c, const TailReq &req, uint32_t *final_cur)
     const am_stamp stamp = {base_abs, c->rate_i, c->tt_dev.p, (uint32_t)c->tt.size()};
     if (sc.sparse && !keep_bursts)
         // bb exists only around the candidates: the 240 soft chips of a hit are recomputed from the scan's samples
-        HIPCHK(c, am_launch_extract_slice_iq(recs, {sc.src, (long long)sc.src_abs0, (long long)sc.src_abs1, c->use_pmf, c->s1, c->spc},
+        HIPCHK(c, am_launch_extract_slice_iq(recs, {sc.src, sc.fmt, (long long)sc.src_abs0, (long long)sc.src_abs1, c->use_pmf, c->s1, c->spc},
                                              c->emit_idx.p, stamp, so, c->stream));
     else
         HIPCHK(c, am_launch_extract_slice(recs, {sc.ref.bb, c->frac ? c->chip_idx.p : nullptr, c->geom.hist0, req.e_off}, c->spc,
@@ -1469,7 +1488,8 @@ static int check_samples(am_ctx *c, const void *raw, uint64_t n, int fmt)
 
 // am_process_iq / am_process_samples, or with `submit` the first half: everything is enqueued, the wait for the scan and
 // what follows it (packets, stream state) is left to am_collect.  submit needs AM_F_FLUSH: batches in flight are independent
-// streams.  fmt: the format of `in` (AM_FMT_CF32: interleaved float32); it matters in step 1 only.
+// streams.  fmt: the format of `in` (AM_FMT_CF32: interleaved float32); it matters in steps 0 and 1 -- and, on the native route
+// (view_fmt), it is the format of everything the scan reads and the next call inherits.
 static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint32_t flags, am_packet *out, uint64_t cap,
                            uint64_t *n_out, bool submit)
 {
@@ -1495,21 +1515,41 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
     c->dom_timed = false;
     c->tail_synced = false;
 
-    // 1. one contiguous device view of [src_abs0, S1): carried tail + new samples
-    const float *src = nullptr;
-    uint64_t src_abs0 = c->total_in;
-    if (c->carry_n == 0 && dev_in && fmt == AM_FMT_CF32) {
-        src = static_cast<const float *>(in);           // zero copy
-    } else if (c->carry_n + n > 0) {
-        ENSURE(c, c->src, (c->carry_n + n) * 2 * sizeof(float));
-        float *d = c->src.p;
+    // 0. the form of the view.  A stream that starts with raw samples where the kernels read them (native_front_end, the switch on)
+    // keeps them raw: view, carried tail and scan are of the input's format.  Every other stream is float32 (the staged form).  A
+    // native stream whose format changes goes on staged from this call: the carried tail is widened once.
+    if (c->total_in == 0 && c->carry_n == 0)
+        c->view_fmt = (fmt != AM_FMT_CF32 && c->raw_fe && !submit && native_front_end(c)) ? fmt : AM_FMT_CF32;
+    else if (c->view_fmt != AM_FMT_CF32 && fmt != c->view_fmt) {
         if (c->carry_n) {
-            HIPCHK(c, hipMemcpyAsync(d, c->carry.p, c->carry_n * 2 * sizeof(float), hipMemcpyDeviceToDevice,
-                                     c->stream));
+            ENSURE(c, c->carry2, c->carry_n * 2 * sizeof(float));
+            hipError_t urc = am_launch_unpack(c->view_fmt, c->carry.p, c->carry_n, c->carry2.p, c->stream);
+            if (urc != hipSuccess) return fail(c, AM_EHIP, "am_k_unpack launch", urc);
+            std::swap(c->carry, c->carry2);
+        }
+        c->view_fmt = AM_FMT_CF32;
+    }
+    const int vfmt = c->view_fmt;
+    const size_t vb = am_sample_bytes(vfmt);                // bytes per sample of the view
+
+    // 1. one contiguous device view of [src_abs0, S1): carried tail + new samples
+    const void *src = nullptr;
+    uint64_t src_abs0 = c->total_in;
+    if (c->carry_n == 0 && dev_in && fmt == vfmt && (vfmt == AM_FMT_CF32 || (reinterpret_cast<uintptr_t>(in) & 15u) == 0)) {
+        src = in;                                           // zero copy (raw: where the unguarded loads of am_k_fe3<FMT> apply)
+    } else if (c->carry_n + n > 0) {
+        ENSURE(c, c->src, (c->carry_n + n) * vb);
+        unsigned char *d = reinterpret_cast<unsigned char *>(c->src.p);
+        if (c->carry_n) {
+            HIPCHK(c, hipMemcpyAsync(d, c->carry.p, c->carry_n * vb, hipMemcpyDeviceToDevice, c->stream));
             src_abs0 = c->carry_abs0;
         }
-        // the new samples behind the carried ones: a copy (float32), or the raw bytes widened into their place (am_k_unpack)
-        if (int rc = unpack_into(c, in, n, fmt, dev_in, d + c->carry_n * 2); rc != AM_OK) return rc;
+        // the new samples behind the carried ones: a copy at their own width (float32, or raw on the native route), or the raw
+        // bytes widened into their place (am_k_unpack)
+        if (vfmt == AM_FMT_CF32) {
+            if (int rc = unpack_into(c, in, n, fmt, dev_in, reinterpret_cast<float *>(d) + c->carry_n * 2); rc != AM_OK) return rc;
+        } else if (n)
+            HIPCHK(c, hipMemcpyAsync(d + c->carry_n * vb, in, n * vb, dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         src = d;
     }
     const uint64_t S1 = c->total_in + n;
@@ -1522,11 +1562,13 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         const uint64_t out_abs0 = (P0 / L) * L;
         const uint64_t out_n = S1 - out_abs0;
         const uint64_t need0 = out_abs0 > LH ? out_abs0 - LH : 0;
-        const float *fsrc = src;
+        const void *fsrc = src;
         uint64_t fsrc_abs0 = src_abs0;
-        {
-            int rc = apply_dcblock(c, &fsrc, &fsrc_abs0, S1, need0);
+        if (vfmt == AM_FMT_CF32) {                          // (the native route: no DC blocker)
+            const float *f = static_cast<const float *>(src);
+            int rc = apply_dcblock(c, &f, &fsrc_abs0, S1, need0);
             if (rc != AM_OK) return rc;
+            fsrc = f;
         }
         if (fsrc_abs0 > need0) return fail(c, AM_EINVAL, "internal: stream history was not carried");
         const uint64_t pad = zero_pad(c->spc_hi);
@@ -1541,7 +1583,7 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         }
         const uint32_t j0 = (uint32_t)(P0 - out_abs0), j1 = (uint32_t)(P1 - out_abs0);
         const double T1 = am_now_us();
-        int rc = run_front_and_candidates(c, fsrc, fsrc_abs0, S1, out_abs0, out_n, bb, avg, j0, j1, true);
+        int rc = run_front_and_candidates(c, fsrc, fsrc_abs0, S1, out_abs0, out_n, bb, avg, j0, j1, true, vfmt);
         if (rc != AM_OK) return rc;
         const double T2 = am_now_us();
         c->ht[0] += T1 - T0; c->ht[1] += T2 - T1;
@@ -1598,8 +1640,8 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
         const uint64_t C0 = blk > hist ? blk - hist : 0;
         const uint64_t keep = S1 - C0;
         if (keep) {
-            ENSURE(c, c->carry2, keep * 2 * sizeof(float));
-            HIPCHK(c, hipMemcpyAsync(c->carry2.p, src + (C0 - src_abs0) * 2, keep * 2 * sizeof(float),
+            ENSURE(c, c->carry2, keep * vb);
+            HIPCHK(c, hipMemcpyAsync(c->carry2.p, static_cast<const unsigned char *>(src) + (C0 - src_abs0) * vb, keep * vb,
                                      hipMemcpyDeviceToDevice, c->stream));
             std::swap(c->carry, c->carry2);
             c->tail_synced = false;
@@ -3109,6 +3151,15 @@ int am_last_timing(am_ctx *c, float *total_ms, float *dom_ms)
 }
 
 int am_last_frontend(const am_ctx *c) { return c ? (int)c->scan.path : AM_EINVAL; }
+
+int am_set_raw_front_end(am_ctx *c, int on)
+{
+    if (!c) return AM_EINVAL;
+    c->raw_fe = on ? 1 : 0;                                 // (read when the next stream starts: process_iq_core)
+    return AM_OK;
+}
+int am_get_raw_front_end(const am_ctx *c) { return c ? c->raw_fe : 0; }
+int am_last_scan_format(const am_ctx *c) { return c ? c->scan.fmt : AM_EINVAL; }
 
 long long am_last_num_candidates(const am_ctx *c)
 {

@@ -27,9 +27,13 @@
 //     traffic; burst extraction now recomputes its 240 chip-spaced samples from IQ (am_kernels.hip).
 //     Plus one number per workgroup: the largest bb of its segment (+inf if any is not finite), the bound the
 //     refinement's exact energy-difference test needs (am_k_cand_d).
+//   * am_k_fe3<FMT>: the samples a radio delivers -- sc16, cs8, cu8 -- are staged as they are, 4 or 2 bytes per
+//     sample instead of 8 and no widening pass in front; only the staging differs (fe3_rstage_step), am_k_fe3<AM_FMT_CF32> is the
+//     kernel the lines above describe.
 //
 // Reference: python/rx_path.py:38-54 (|.|^2, moving averages), lib/preamble_impl.cc:172-179 (test).
 #include "am_fe_stream.h"
+#include "am_raw_iq.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -73,7 +77,7 @@
 #define FE3_BBW 17                        /* chips of bb kept from a candidate's chip on (am_k_cand reads up to pos + 16*spc) */
 
 struct am_fe3_args {
-    const float *iq;
+    const float *iq;                      // am_k_fe3<AM_FMT_CF32>: interleaved float32; the other instantiations: raw samples of their format
     long long src_abs0, src_abs1;         // absolute range of samples present in iq
     long long out_abs0;                   // absolute index of array coordinate 0 (multiple of 48*spc)
     long long out_n;                      // array coordinates with data
@@ -217,6 +221,108 @@ __device__ __forceinline__ void fe3_stage_step(const am_fe3_args &a, const fe3_s
     fe3_raw v;
     fe3_load_step<J0>(a, A0, tid, v);
     fe3_store_step<J0>(L, slot0, par, tid, v);
+}
+
+// ---- raw integer samples (am_k_fe3<AM_FMT_SC16 / CS8 / CU8>): the same staging from 16-byte pieces of SPP = 4 or 8 samples ----------
+// Piece q = tid + 128 j holds samples SPP q .. of the step, which lie in chip q / PPC (PPC = 32 / SPP pieces per chip): the thread
+// owns chips c0 + CPR j (c0 = tid / PPC, CPR = 128 / PPC = 4 SPP chips per round of pieces), NL = 96 / CPR loads per step instead
+// of 12, and stores SPP floats of |.|^2 per piece into the ring row.  The conversion is am_raw_iq.h's, so every |.|^2 is the one
+// am_k_fe3<AM_FMT_CF32> forms from am_k_unpack's floats, bit for bit; everything behind the staged ring is the same code.
+template <int FMT> struct fe3_rg {
+    static constexpr int BPS = 2 * unp_fmt<FMT>::CS;                  // bytes per sample: 4, 2
+    static constexpr int SPP = 16 / BPS;                              // samples per piece: 4, 8
+    static constexpr int PPC = FE3_SPC / SPP;                         // pieces per chip: 8, 4
+    static constexpr int CPR = FE3_NT / PPC;                          // chips per round of pieces: 16, 32
+    static constexpr int NL = FE3_S / CPR;                            // pieces per thread and step: 6, 3
+    static constexpr int WARM_J0 = (FE3_S - FE3_LAG - AM_CHIPS_AVG) / CPR;   // pieces the ring-rebuilding step does not load
+    static_assert(FE3_SPC % SPP == 0 && FE3_NT % PPC == 0 && FE3_S % CPR == 0 && (CPR & (CPR - 1)) == 0, "whole rounds of pieces");
+};
+template <int FMT> struct fe3_rraw { uint4 v[fe3_rg<FMT>::NL]; };
+
+template <int FMT, int J0>
+__device__ __forceinline__ void fe3_rload_step(const am_fe3_args &a, long long A0, int tid, fe3_rraw<FMT> &r)
+{
+    typedef fe3_rg<FMT> G;
+    const unsigned char *gb = reinterpret_cast<const unsigned char *>(a.iq) + (size_t)(A0 - a.src_abs0) * G::BPS;
+    const unsigned off = (unsigned)tid * 16u;
+#pragma unroll
+    for (int j = J0; j < G::NL; ++j) {
+        // (as fe3_load_step: scalar base per pair of pieces, the lane's 32-bit offset, 2 KB as the instruction's immediate)
+        unsigned long long g = reinterpret_cast<unsigned long long>(gb + (size_t)(j & ~1) * (FE3_NT * 16u));
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("" : "+s"(g));
+#endif
+        r.v[j] = fes_gload16u_at(g, off + (unsigned)(j & 1) * (FE3_NT * 16u));
+    }
+}
+
+struct fe3_rdest { float *row, *roww; int jw, c0; float *m47, *mp; };
+template <int FMT>
+__device__ __forceinline__ fe3_rdest fe3_rdest_of(const fe3_smem &L, int slot0, int par, int tid)
+{
+    typedef fe3_rg<FMT> G;
+    const int c0 = tid / G::PPC, k = tid & (G::PPC - 1);
+    const int sc = slot0 + c0;                                        // < FE3_CR + CPR
+    fe3_rdest d;
+    d.c0 = c0;
+    d.jw = (FE3_CR + G::CPR - 1 - sc) / G::CPR;                       // slot0 + c0 + CPR j >= FE3_CR  <=>  j >= jw
+    d.row = L.X + fes_mul24(sc, FE3_XS) + G::SPP * k;
+    d.roww = d.row - FE3_CR * FE3_XS;
+    d.m47 = L.M47 + G::SPP * k;
+    d.mp = L.MP + par * 32 + G::SPP * k;
+    return d;
+}
+// (j: a constant in the unrolled loops, where the tests on the chip fold to one compare of c0 for the pieces that can hold chip
+// 47 or 95 and to nothing for the others)
+template <int FMT>
+__device__ __forceinline__ void fe3_rstore_piece(const fe3_rdest &d, int j, const float *mm)
+{
+    typedef fe3_rg<FMT> G;
+    float *dst = ((j >= d.jw) ? d.roww : d.row) + j * (G::CPR * FE3_XS);
+    float *second = nullptr;
+    const int chip = d.c0 + G::CPR * j;
+#pragma unroll
+    for (int w = 1; w <= FE3_NW; ++w)
+        if (chip == AM_CHIPS_AVG * w - 1) second = (w < FE3_NW) ? d.m47 + (w - 1) * 32 : d.mp;
+#pragma unroll
+    for (int q = 0; q < G::SPP / 4; ++q) {
+        float4 u;
+        u.x = mm[4 * q]; u.y = mm[4 * q + 1]; u.z = mm[4 * q + 2]; u.w = mm[4 * q + 3];
+        reinterpret_cast<float4 *>(dst)[q] = u;
+        if (second) reinterpret_cast<float4 *>(second)[q] = u;
+    }
+}
+template <int FMT, bool GUARD, int J0>
+__device__ __forceinline__ void fe3_rstage_step(const am_fe3_args &a, const fe3_smem &L, long long A0, int slot0, int par, int tid)
+{
+    typedef fe3_rg<FMT> G;
+    const fe3_rdest d = fe3_rdest_of<FMT>(L, slot0, par, tid);
+    if constexpr (GUARD) {
+        // stream edges / a step whose first byte is not 16-byte aligned: one sample at a time, zeros outside the stream
+#pragma unroll 1
+        for (int j = 0; j < G::NL; ++j) {
+            const long long n0 = A0 + (long long)G::SPP * (long long)(tid + FE3_NT * j);
+            float mm[G::SPP];
+#pragma unroll
+            for (int i = 0; i < G::SPP; ++i) {
+                const long long n = n0 + i;
+                mm[i] = 0.0f;
+                if (n >= a.src_abs0 && n < a.src_abs1) mm[i] = raw_mag2_at<FMT>(a.iq, n - a.src_abs0);
+            }
+            fe3_rstore_piece<FMT>(d, j, mm);
+        }
+        return;
+    }
+    fe3_rraw<FMT> v;
+    fe3_rload_step<FMT, J0>(a, A0, tid, v);
+#pragma unroll
+    for (int j = J0; j < G::NL; ++j) {
+        float mm[G::SPP];
+        const uint32_t w[4] = {v.v[j].x, v.v[j].y, v.v[j].z, v.v[j].w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) raw_word_mag2<FMT>(w[q], mm + q * (G::SPP / 4));
+        fe3_rstore_piece<FMT>(d, j, mm);
+    }
 }
 
 // One step (its |.|^2 is staged).
@@ -589,6 +695,9 @@ __device__ __forceinline__ void fe3_step(const am_fe3_args &a, const fe3_smem &L
     }
 }
 
+// FMT: the format of the samples at a.iq.  Only the staging differs; am_k_fe3<AM_FMT_CF32> is the kernel as it was before the other
+// three existed (tools/isa_compare.py, profiles/raw_front_end/isa_cf32_kernels.txt).
+template <int FMT>
 __global__ void __launch_bounds__(FE3_NT, FE3_WPS) am_k_fe3(am_fe3_args a)
 {
     HIP_DYNAMIC_SHARED(unsigned char, smem);
@@ -645,11 +754,18 @@ __global__ void __launch_bounds__(FE3_NT, FE3_WPS) am_k_fe3(am_fe3_args a)
         // (the ring slots about to be staged were read by the previous step's phase B: its last barrier is behind us)
         // load, wait, stage.  The step before the segment only feeds the rings: the first chip tested is chip
         // FE3_S - FE3_LAG of it, whose reference level reaches back 47 chips -- chips below FE3_WARM_J0 * 8 stay zero
-        if (have) {
-            if (test) fe3_stage_step<false>(a, L, a.out_abs0 + (long long)step * FE3_T, slot0, par, tid);
-            else fe3_stage_step<false, FE3_WARM_J0>(a, L, a.out_abs0 + (long long)step * FE3_T, slot0, par, tid);
-        } else
-            fe3_stage_step<true>(a, L, a.out_abs0 + (long long)step * FE3_T, slot0, par, tid);
+        if constexpr (FMT == AM_FMT_CF32) {
+            if (have) {
+                if (test) fe3_stage_step<false>(a, L, a.out_abs0 + (long long)step * FE3_T, slot0, par, tid);
+                else fe3_stage_step<false, FE3_WARM_J0>(a, L, a.out_abs0 + (long long)step * FE3_T, slot0, par, tid);
+            } else
+                fe3_stage_step<true>(a, L, a.out_abs0 + (long long)step * FE3_T, slot0, par, tid);
+        } else {
+            const long long A0 = a.out_abs0 + (long long)step * FE3_T;
+            if (!have) fe3_rstage_step<FMT, true, 0>(a, L, A0, slot0, par, tid);
+            else if (test) fe3_rstage_step<FMT, false, 0>(a, L, A0, slot0, par, tid);
+            else fe3_rstage_step<FMT, false, fe3_rg<FMT>::WARM_J0>(a, L, A0, slot0, par, tid);
+        }
         FE3_STAMP(5);
         fes_barrier();                                                // B1: |.|^2 of this step staged
         FE3_STAMP(0);
@@ -712,25 +828,38 @@ hipError_t am_launch_fe3(const am_fe_stream_req &r, am_fe_layout *layout, hipStr
     fes_fill_args(a, r, l);
     a.n_long = l.n_long;
     const unsigned grid = l.nwg;
-    static std::atomic<bool> attr_done[64];
+    const void *kernel = nullptr;
+    switch (r.fmt) {
+    case AM_FMT_CF32: kernel = reinterpret_cast<const void *>(&am_k_fe3<AM_FMT_CF32>); break;
+    case AM_FMT_SC16: kernel = reinterpret_cast<const void *>(&am_k_fe3<AM_FMT_SC16>); break;
+    case AM_FMT_CS8: kernel = reinterpret_cast<const void *>(&am_k_fe3<AM_FMT_CS8>); break;
+    case AM_FMT_CU8: kernel = reinterpret_cast<const void *>(&am_k_fe3<AM_FMT_CU8>); break;
+    default: return hipErrorInvalidValue;
+    }
+    static std::atomic<bool> attr_done[64][4];
+    static_assert(AM_FMT_CF32 >= 0 && AM_FMT_CF32 < 4 && AM_FMT_SC16 < 4 && AM_FMT_CS8 < 4 && AM_FMT_CU8 < 4, "format codes index attr_done");
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_done[dev].load(std::memory_order_acquire)) {
-        hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&am_k_fe3),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)FE3_LDS_BYTES);
+    if (dev < 0 || dev >= 64 || !attr_done[dev][r.fmt].load(std::memory_order_acquire)) {
+        hipError_t rc = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FE3_LDS_BYTES);
         if (rc != hipSuccess) return rc;
-        if (dev >= 0 && dev < 64) attr_done[dev].store(true, std::memory_order_release);
+        if (dev >= 0 && dev < 64) attr_done[dev][r.fmt].store(true, std::memory_order_release);
     }
 #if defined(FE3_PROFILE)
     // blocking; prints mean cycles per step and phase (wave 0 / wave 1) -- never in the default build
     if (hipMalloc(reinterpret_cast<void **>(&a.prof), (size_t)grid * FE3_NW * 12 * sizeof(long long)) != hipSuccess) a.prof = nullptr;
 #endif
-    hipLaunchKernelGGL(am_k_fe3, dim3(grid), dim3(FE3_NT), FE3_LDS_BYTES, s, a);
+    switch (r.fmt) {
+    case AM_FMT_SC16: hipLaunchKernelGGL(am_k_fe3<AM_FMT_SC16>, dim3(grid), dim3(FE3_NT), FE3_LDS_BYTES, s, a); break;
+    case AM_FMT_CS8: hipLaunchKernelGGL(am_k_fe3<AM_FMT_CS8>, dim3(grid), dim3(FE3_NT), FE3_LDS_BYTES, s, a); break;
+    case AM_FMT_CU8: hipLaunchKernelGGL(am_k_fe3<AM_FMT_CU8>, dim3(grid), dim3(FE3_NT), FE3_LDS_BYTES, s, a); break;
+    default: hipLaunchKernelGGL(am_k_fe3<AM_FMT_CF32>, dim3(grid), dim3(FE3_NT), FE3_LDS_BYTES, s, a); break;
+    }
     hipError_t lrc = hipGetLastError();
 #if defined(FE3_PROFILE)
     if (a.prof) {
         int occ = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(&am_k_fe3), FE3_NT, FE3_LDS_BYTES);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, FE3_NT, FE3_LDS_BYTES);
         fprintf(stderr, "fe3: grid %u, %u steps per workgroup, %d bytes of LDS, runtime says %d workgroups per CU\n", grid, l.spw,
                 (int)FE3_LDS_BYTES, occ);
         std::vector<long long> h((size_t)grid * FE3_NW * 12);

@@ -836,6 +836,7 @@ __global__ void __launch_bounds__(AM_WAVE * NW, (fe4_cfg<SPC, G, NW>::MINW)) am_
 #else
 #define FE4_USE_FE3(spc) ((spc) == 32)
 #endif
+int am_fe4_uses_fe3(int spc) { return FE4_USE_FE3(spc) ? 1 : 0; }
 // the specialisations that exist: chips per lane and waves per workgroup by samples per chip
 static int fe4_g_of(int spc)
 {
@@ -971,6 +972,7 @@ hipError_t am_launch_fe4(int spc, const am_fe_stream_req &r, am_fe_layout *layou
 {
     if (!am_fe4_supported(spc)) return hipErrorInvalidValue;
     if (FE4_USE_FE3(spc)) return am_launch_fe3(r, layout, s, wgs_per_cu, levelled);
+    if (r.fmt != AM_FMT_CF32) return hipErrorInvalidValue;            // (am_k_fe4 reads float32 only)
     if (am_fe4_steps(r.out_n, spc) == 0) { *layout = am_fe_plan(spc, r.out_n, 1, false); return hipSuccess; }   // nothing to launch
     switch (spc) {
     case 1: return fe4_launch<1, 24, 2>(r, layout, s, wgs_per_cu);

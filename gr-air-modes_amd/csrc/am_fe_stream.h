@@ -134,6 +134,20 @@ __device__ __forceinline__ float4 fes_gload16_at(unsigned long long base, unsign
 #endif
 }
 
+// ... as four 32-bit words: raw integer samples (am_k_fe3<FMT>, am_raw_iq.h)
+__device__ __forceinline__ uint4 fes_gload16u_at(unsigned long long base, unsigned off)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef unsigned fes_u4 __attribute__((ext_vector_type(4)));
+    typedef const fes_u4 __attribute__((address_space(1))) *gp;
+    const fes_u4 t = __builtin_nontemporal_load(reinterpret_cast<gp>(base + (unsigned long long)off));
+    uint4 r; r.x = t.x; r.y = t.y; r.z = t.z; r.w = t.w;
+    return r;
+#else
+    return *reinterpret_cast<const uint4 *>(base + (unsigned long long)off);
+#endif
+}
+
 // the same with the default cache policy (samples that another kernel reads again soon: am_k_gather_wg's rows)
 __device__ __forceinline__ float4 fes_gload16_cached_at(unsigned long long base, unsigned off)
 {
@@ -177,16 +191,18 @@ static inline long long fes_ceil_div(long long x, long long d) { return -fes_flo
 template <class A>
 static inline void fes_fill_args(A &a, const am_fe_stream_req &r, const am_fe_layout &l)
 {
-    a.iq = r.iq; a.src_abs0 = r.src_abs0; a.src_abs1 = r.src_abs1; a.out_abs0 = r.out_abs0; a.out_n = r.out_n;
+    a.iq = static_cast<decltype(a.iq)>(r.iq); a.src_abs0 = r.src_abs0; a.src_abs1 = r.src_abs1; a.out_abs0 = r.out_abs0; a.out_n = r.out_n;
     a.bb_sparse = r.bb_sparse; a.avg_sparse = r.avg_sparse; a.j0 = r.j0; a.j1 = r.j1;
     a.bits = r.bits; a.wg_cnt = r.wg_cnt; a.wg_max = r.wg_max;
     a.use_pmf = r.use_pmf ? 1 : 0; a.s1 = r.s1; a.sL = r.sL; a.thr_lin = r.thr_lin;
     a.nsteps = l.nsteps; a.steps_per_wg = l.spw;
     a.prof = nullptr;
     const long long T = l.tile, lag = l.lag;
-    // steps loaded without guards: samples [out_abs0 + k T, + T) inside [src_abs0, src_abs1), source 16-byte aligned (the parity
-    // of the offset is the same for every step when T is even: am_k_fe3's 3072 is)
-    const bool aligned = ((reinterpret_cast<uintptr_t>(r.iq) + (uintptr_t)(r.out_abs0 - r.src_abs0) * 8u) & 15u) == 0 && (T % 2) == 0;
+    // steps loaded without guards: samples [out_abs0 + k T, + T) inside [src_abs0, src_abs1), the step's first BYTE 16-byte
+    // aligned (the same for every step when a step is a multiple of 16 bytes: am_k_fe3's 3072 samples are, in every format)
+    const uintptr_t bps = r.fmt == AM_FMT_CF32 ? 8u : (r.fmt == AM_FMT_SC16 ? 4u : 2u);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(r.iq) + (uintptr_t)(r.out_abs0 - r.src_abs0) * bps) & 15u) == 0 &&
+                         ((uintptr_t)T * bps) % 16u == 0;
     auto clampi = [](long long v) { return (int)(v < -4 ? -4 : (v > 0x7FFFFFF0ll ? 0x7FFFFFF0ll : v)); };
     a.raw_lo = clampi(fes_ceil_div(r.src_abs0 - r.out_abs0, T));
     a.raw_hi = aligned ? clampi(fes_floor_div(r.src_abs1 - r.out_abs0, T)) : a.raw_lo;

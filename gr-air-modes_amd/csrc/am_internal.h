@@ -166,6 +166,7 @@ unsigned am_fe4_waves(int spc);             /* segments (waves) per step        
 unsigned am_fe4_tile(int spc);              /* positions per step                                               */
 unsigned am_fe4_lag(int spc);
 unsigned am_fe4_steps(long long out_n, int spc);
+int am_fe4_uses_fe3(int spc);               /* am_launch_fe4 runs am_k_fe3<FMT> at this rate (64 Msps, product configuration) */
 unsigned am_fe3_waves(void);                /* am_k_fe3's segments (48 chips = 48 bitmap words each) per step   */
 
 /* The bitmap a streaming front end leaves and who made which part of it: workgroup g took a contiguous run of steps and formed
@@ -197,7 +198,8 @@ am_fe_layout am_fe_plan(int spc, long long out_n, unsigned resident, bool levell
 
 /* what a streaming front end is launched for (the fields am_fe3_args / am_fe4_args describe) */
 struct am_fe_stream_req {
-    const float *iq;
+    const void *iq;                       /* samples of format fmt: am_k_fe3<FMT> reads them as they are; am_k_fe4: AM_FMT_CF32 only */
+    int fmt;
     long long src_abs0, src_abs1, out_abs0, out_n;
     float *bb_sparse, *avg_sparse;        /* (bb_sparse null: am_k_fe3 writes no rows)                       */
     uint32_t j0, j1;
@@ -221,7 +223,8 @@ hipError_t am_launch_fe4(int spc, const am_fe_stream_req &r, am_fe_layout *layou
 /* rows != null && rows->iq (64 Msps: am_k_fe3 no longer writes them): the same launch also forms, from the samples, the bb rows
  * the refinement reads -- the 17 chips from every candidate's chip on, canonical order (am_rows_segment32). */
 struct am_rows_args {
-    const float *iq;                      /* null: no rows (the front end wrote them: am_k_fe4 rates)        */
+    const void *iq;                       /* null: no rows (the front end wrote them: am_k_fe4 rates)        */
+    int fmt;                              /* AM_FMT_* of iq (am_k_refine_seg<PMF, FMT>; am_k_gather_wg: AM_FMT_CF32 only) */
     long long src_abs0, src_abs1;         /* absolute range of samples present in iq                        */
     long long out_abs0;                   /* absolute index of array coordinate 0                           */
     long long out_n;                      /* array coordinates with data (nothing is stored at or beyond)   */
@@ -415,7 +418,8 @@ hipError_t am_launch_extract_slice(const am_records &r, const am_dense_src &src,
                                    const am_slice_out &o, hipStream_t s);
 /* the same when bb exists only around the candidates: the burst is recomputed from IQ (iq[0] = absolute sample src_abs0) */
 struct am_iq_src {
-    const float *iq;
+    const void *iq;
+    int fmt;                   /* AM_FMT_* of iq; other than AM_FMT_CF32 at 32 samples per chip only (am_k_extract_slice_iq<32, ..., 1>) */
     long long src_abs0, src_abs1;
     int use_pmf;
     float s1;

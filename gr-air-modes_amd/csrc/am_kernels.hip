@@ -19,6 +19,7 @@
 #include "am_internal.h"
 #include "am_dispatch.h"
 #include "am_fe_stream.h"
+#include "am_raw_iq.h"
 
 // keeps a loaded value where it is in the program (the compiler otherwise sinks loads to their first use, behind branches)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -2513,21 +2514,41 @@ extern "C" int am_debug_xprof(unsigned long long *out, int reset)
 #endif
 
 // |.|^2 of absolute sample w, zero outside the source
-__device__ __forceinline__ float am_mag_guarded(const float2 *__restrict__ iq2, long long src_abs0, long long src_abs1, long long w)
+// (RAW, here and below: the source holds raw samples of format fmt, a wave-uniform run-time value -- am_raw_iq.h; RAW = 0 is the
+// code as it was before the raw formats, and fmt is not looked at)
+template <int RAW = 0>
+__device__ __forceinline__ float am_mag_guarded(const float2 *__restrict__ iq2, long long src_abs0, long long src_abs1, long long w, int fmt = 0)
 {
     float mm = 0.0f;
+    if constexpr (RAW != 0) {
+        if (w >= src_abs0 && w < src_abs1) mm = raw_mag2_at_rt(fmt, iq2, w - src_abs0);
+        return mm;
+    }
     if (w >= src_abs0 && w < src_abs1) { const float2 t = iq2[w - src_abs0]; const float r = t.x * t.x, q = t.y * t.y; mm = r + q; }
     return mm;
 }
 
 // soft chip c of the burst whose first sample has absolute index ae (bb; the reference level comes off later).
 // inside (uniform): every lane's 16-byte loads lie inside the source -- all but the hits at the two ends of the stream
-template <int SPC>
+// (RAW: never `inside` -- at 32 samples per chip, the only rate with raw samples, those hits go through am_stage_energies32)
+template <int SPC, int RAW = 0>
 __device__ __forceinline__ float am_soft_chip_iq(const float *__restrict__ iq, long long src_abs0, long long src_abs1,
-                                                 bool pmf, float s1, long long ae, int c, bool inside)
+                                                 bool pmf, float s1, long long ae, int c, bool inside, int fmt = 0)
 {
     const float2 *iq2 = reinterpret_cast<const float2 *>(iq);
     const long long n = ae + (long long)c * SPC;                              // the sample this lane forms
+    if constexpr (RAW != 0) {
+        if (!pmf) return am_mag_guarded<1>(iq2, src_abs0, src_abs1, n, fmt);
+        const int ii = (int)(ae % SPC);
+        float pre = 0.0f, suf = 0.0f;
+#pragma unroll 1
+        for (long long w = n - ii; w <= n; ++w) pre = pre + am_mag_guarded<1>(iq2, src_abs0, src_abs1, w, fmt);
+#pragma unroll 1
+        for (long long w = n - ii - 1; w >= n - SPC + 1; --w) suf = suf + am_mag_guarded<1>(iq2, src_abs0, src_abs1, w, fmt);
+        float v = (ii == SPC - 1) ? pre * s1 : (suf + pre) * s1;
+        if (n >= src_abs1) v = 0.0f;
+        return v;
+    }
     if (!pmf) {
         float v = 0.0f;
         if (n >= src_abs0 && n < src_abs1) {
@@ -2594,12 +2615,39 @@ __device__ __forceinline__ float am_soft_chip_iq(const float *__restrict__ iq, l
 // five bits say whether the packet is a long one -- no second memory round trip behind the decision -- measured 43.8 against 40.0 us
 // at the bench density, 20.9 against 18.7 at 2 000 bursts/s: 28 more registers and 47 % more bytes for every short packet cost more
 // than the round trip; profiles/r5_fe64.  Not kept.)
-template <int NS>
-__device__ __forceinline__ void am_stage_energies32(const float *__restrict__ iq, long long src_abs0, long long B0, float *E, int tid)
+// (RAW: the same pieces -- a pair of samples per thread and round -- as loads of 8 bytes of sc16 or 4 of cs8 / cu8; the source is
+// aligned to a pair)
+template <int NS, int RAW = 0>
+__device__ __forceinline__ void am_stage_energies32(const float *__restrict__ iq, long long src_abs0, long long B0, float *E, int tid, int fmt = 0)
 {
     static_assert(NS % 512 == 0, "whole rounds of 256 threads x 2 samples");
     constexpr int ROUNDS = NS / 512;
     const int odd = (int)((B0 - src_abs0) & 1);
+    if constexpr (RAW != 0) {
+        const long long p0 = (B0 - odd - src_abs0) >> 1;              // the first pair
+        const int i0 = 2 * tid - odd, i1 = i0 + 1;
+        float *const e0 = E + (i0 >> 5) * AM_XROW + (i0 & 31);
+        float *const e1 = E + (i1 >> 5) * AM_XROW + (i1 & 31);
+        auto run = [&](auto f) __attribute__((always_inline)) {
+            constexpr int F = decltype(f)::value;
+            raw_pair_bits v[ROUNDS], vx;
+#pragma unroll
+            for (int r = 0; r < ROUNDS; ++r) v[r] = raw_pair_load<F>(iq, p0 + tid + 256 * r);
+            vx.lo = vx.hi = 0u;
+            if (odd && tid == 0) vx = raw_pair_load<F>(iq, p0 + NS / 2);
+#pragma unroll
+            for (int r = 0; r < ROUNDS; ++r) {
+                const float2 m = raw_pair_mag2<F>(v[r]);
+                if (r > 0 || i0 >= 0) e0[r * 16 * AM_XROW] = m.x;
+                e1[r * 16 * AM_XROW] = m.y;
+            }
+            if (odd && tid == 0) E[((NS - 1) >> 5) * AM_XROW + 31] = raw_pair_mag2<F>(vx).x;
+        };
+        if (fmt == AM_FMT_SC16) run(std::integral_constant<int, AM_FMT_SC16>{});          // (uniform)
+        else if (fmt == AM_FMT_CS8) run(std::integral_constant<int, AM_FMT_CS8>{});
+        else run(std::integral_constant<int, AM_FMT_CU8>{});
+        return;
+    }
     const float4 *src = reinterpret_cast<const float4 *>(iq) + ((B0 - odd - src_abs0) >> 1);
     const int i0 = 2 * tid - odd, i1 = i0 + 1;                        // samples of the thread's piece in round 0 (i0 = -1: not wanted)
     float *const e0 = E + (i0 >> 5) * AM_XROW + (i0 & 31);            // (arithmetic shift: -1 -> row -1, column 31: right from round 1 on)
@@ -2639,7 +2687,9 @@ __device__ __forceinline__ float am_soft_chip_row32(const float *E, int row, int
 #ifndef AM_XS_WPS
 #define AM_XS_WPS 8                       /* waves per SIMD the extraction kernel is compiled for (64 VGPRs, no spills: eight workgroups per CU, 2 048 hits in flight) */
 #endif
-template <int SPC, int FIX, int GATE, int LF>
+// RAW = 1 (32 samples per chip only): the source holds raw samples whose format comes in bits 8.. of use_pmf -- a run-time value, the
+// same in every lane, so that the instantiations are not multiplied by the formats; RAW = 0 is the kernel as it was before.
+template <int SPC, int FIX, int GATE, int LF, int RAW>
 __global__ void __launch_bounds__(256, AM_XS_WPS)
 am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long long src_abs1, int use_pmf, float s1,
                       const float *__restrict__ inavg, const uint4 *__restrict__ emit_idx,
@@ -2668,8 +2718,9 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
         host_out[AM_PW_CANDIDATES] = Mp ? *Mp : 0u;
         host_out[AM_PW_CHAIN_ERR] = scalars[AM_SW_CHAIN_ERR];                            // a chained scan of this step gave up (am_chain_prefix)
     }
-    const bool pmf = use_pmf != 0;
-    const bool wide = (reinterpret_cast<uintptr_t>(iq) & 15u) == 0;
+    const bool pmf = RAW != 0 ? (use_pmf & 1) != 0 : use_pmf != 0;
+    const int fmt = RAW != 0 ? use_pmf >> 8 : 0;
+    const bool wide = (reinterpret_cast<uintptr_t>(iq) & (RAW != 0 ? (fmt == AM_FMT_SC16 ? 7u : 3u) : 15u)) == 0;
     uint32_t lf_word = 0u;                                    // am_set_long_formats: the enabled formats (<..., 0> never reads them)
     if constexpr (LF > 0) lf_word = scalars[AM_SW_LONG_FMT];
     // (Giving every XCD one contiguous eighth of the hits, so that the overlapping windows of neighbouring hits meet
@@ -2695,14 +2746,14 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
         const int ii = (int)(ae % SPC);
         if constexpr (SPC == 32) {
             if (staged) {
-                am_stage_energies32<HEAD * 32>(iq, src_abs0, ae - (SPC - 1), stg, tid);
+                am_stage_energies32<HEAD * 32, RAW>(iq, src_abs0, ae - (SPC - 1), stg, tid, fmt);
                 __syncthreads();
             }
         }
         if (tid < HEAD) {
             float v;
             if (staged) v = am_soft_chip_row32(stg, tid, ii, s1) - av;
-            else v = am_soft_chip_iq<SPC>(iq, src_abs0, src_abs1, pmf, s1, ae, tid, inside) - av;   // preamble_impl.cc:219-221
+            else v = am_soft_chip_iq<SPC, RAW>(iq, src_abs0, src_abs1, pmf, s1, ae, tid, inside, fmt) - av;   // preamble_impl.cc:219-221
             sb[tid] = v;
             if (bursts_out) bursts_out[(size_t)i * AM_BURST + tid] = v;
         }
@@ -2713,7 +2764,7 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
         const bool all = bursts_out != nullptr || am_burst_is_long<LF>(sb, lf_word);
         if constexpr (SPC == 32) {
             if (staged && all) {                                              // (the rows' readers are behind the barrier above)
-                am_stage_energies32<(AM_BURST - HEAD) * 32>(iq, src_abs0, ae - (SPC - 1) + (long long)HEAD * SPC, stg, tid);
+                am_stage_energies32<(AM_BURST - HEAD) * 32, RAW>(iq, src_abs0, ae - (SPC - 1) + (long long)HEAD * SPC, stg, tid, fmt);
                 __syncthreads();
             }
         }
@@ -2721,7 +2772,7 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
             float v = 0.0f;                                                   // (never looked at in a short packet)
             if (all) {
                 if (staged) v = am_soft_chip_row32(stg, tid - HEAD, ii, s1) - av;
-                else v = am_soft_chip_iq<SPC>(iq, src_abs0, src_abs1, pmf, s1, ae, tid, inside) - av;
+                else v = am_soft_chip_iq<SPC, RAW>(iq, src_abs0, src_abs1, pmf, s1, ae, tid, inside, fmt) - av;
                 if (bursts_out) bursts_out[(size_t)i * AM_BURST + tid] = v;
             }
             sb[tid] = v;
@@ -2749,7 +2800,7 @@ am_k_extract_slice_iq(const float *__restrict__ iq, long long src_abs0, long lon
 #endif
 }
 
-template <int SPC, int FIX, int GATE, int LF> struct am_xs_iq_key {};     // (names an instantiation's occupancy cache)
+template <int SPC, int FIX, int GATE, int LF, int RAW> struct am_xs_iq_key {};     // (names an instantiation's occupancy cache)
 
 hipError_t am_launch_extract_slice_iq(const am_records &r, const am_iq_src &src, const uint4 *emit_idx, const am_stamp &st,
                                       const am_slice_out &o, hipStream_t s)
@@ -2758,24 +2809,34 @@ hipError_t am_launch_extract_slice_iq(const am_records &r, const am_iq_src &src,
     int dev = 0;
     (void)hipGetDevice(&dev);
     const int use_pmf = src.spc == 1 ? 0 : src.use_pmf;       // (a one-sample window is the sample itself: s1 = 1)
+    const bool raw = src.fmt != AM_FMT_CF32;
+    if (raw && (src.spc != 32 || am_sample_bytes(src.fmt) == 0)) return hipErrorInvalidValue;      // (no such instantiation)
     const bool known = am_with_spc(src.spc, [&](auto spc) {
         am_with_fix_gate_long(o.fix_bits, o.gate, o.long_mask, [&](auto fix, auto gate, auto lf) {
             constexpr int S = decltype(spc)::value, F = decltype(fix)::value, G = decltype(gate)::value, L = decltype(lf)::value;
+            auto launch = [&](auto rawc) {
+            constexpr int R = decltype(rawc)::value;
             // workgroups of 256 threads per CU: what the instantiation's registers allow (five at 32 samples per chip, where a
             // lane holds a 34-sample window; eight at one or two samples per chip, where the kernel is a chain of memory round
             // trips per hit and more hits in flight is all that helps), asked of the runtime once per device and instantiation
-            std::atomic<int> *cached = am_device_cache<am_xs_iq_key<S, F, G, L>>(dev);
+            std::atomic<int> *cached = am_device_cache<am_xs_iq_key<S, F, G, L, R>>(dev);
             int w = cached ? cached->load(std::memory_order_acquire) : 0;
             if (w <= 0) {
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, F, G, L>), 256, 0) != hipSuccess || w <= 0) w = 5;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&w, reinterpret_cast<const void *>(&am_k_extract_slice_iq<S, F, G, L, R>), 256, 0) != hipSuccess || w <= 0) w = 5;
                 w = w > 8 ? 8 : w;
                 if (cached) cached->store(w, std::memory_order_release);
             }
             const uint32_t resident = (uint32_t)w * (uint32_t)am_device_cus();
             const uint32_t grid = o.n_max < resident ? o.n_max : resident;
-            hipLaunchKernelGGL((am_k_extract_slice_iq<S, F, G, L>), dim3(grid), dim3(256), 0, s, src.iq, src.src_abs0, src.src_abs1, use_pmf,
+            hipLaunchKernelGGL((am_k_extract_slice_iq<S, F, G, L, R>), dim3(grid), dim3(256), 0, s, static_cast<const float *>(src.iq), src.src_abs0,
+                               src.src_abs1, R != 0 ? ((use_pmf ? 1 : 0) | (src.fmt << 8)) : use_pmf,
                                src.s1, r.inavg, emit_idx, o.n_ptr, r.pos, r.e, st.base_abs, st.rate, st.tt, st.ntt, o.bursts_out,
                                o.tags_out, o.crc_pow, o.packets, o.scalars, o.host_out, o.Mp);
+            };
+            if constexpr (S == 32) {
+                if (raw) { launch(std::integral_constant<int, 1>{}); return; }
+            }
+            launch(std::integral_constant<int, 0>{});
         });
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;

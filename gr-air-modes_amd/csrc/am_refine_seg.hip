@@ -29,6 +29,7 @@
 // oracle's candidate records (stage-level parity tests, every record).
 #include "am_internal.h"
 #include "am_fe_stream.h"
+#include "am_raw_iq.h"
 
 #include <stdio.h>
 
@@ -100,7 +101,7 @@ struct am_rseg_args {
     const float *wg_max;
     uint32_t nwg, words_per_wg, nwords, Mcap, vspan, nv, end_j, parts, pw;
     uint32_t n_long, words_short, vspan_short;   // segments n_long .. : words_short words, vspan_short array coordinates each (levelled front end)
-    const float *iq;
+    const float *iq;                      // am_k_refine_seg<PMF, AM_FMT_CF32>: float32; the other instantiations: raw samples of their format
     long long src_abs0, src_abs1, out_abs0;
     const float *avg_sparse;
     float s1, thr_lin;
@@ -207,7 +208,10 @@ struct rs_batch {
     float4 v[RS_MAXR];
 };
 
-template <bool PMF>
+// FMT: the format of the samples at a.iq.  A raw format's rows are loaded a PAIR of samples per lane and round -- 8 bytes of sc16, 4
+// of cs8 / cu8, where float32 takes 16 -- and widened by am_raw_iq.h's helpers when the loads have arrived: the same pieces, the
+// same rows, the same |.|^2 bit for bit.  am_k_refine_seg<PMF, AM_FMT_CF32> is the kernel as it was before the others existed.
+template <bool PMF, int FMT>
 __global__ void __launch_bounds__(RS_NT, RS_WPS) am_k_refine_seg(am_rseg_args a)
 {
     constexpr int SPC = 32;
@@ -285,7 +289,9 @@ __global__ void __launch_bounds__(RS_NT, RS_WPS) am_k_refine_seg(am_rseg_args a)
     if (pb >= seg_e) return;                                   // (uniform)
     RS_STAMP(0);                                               // counts + first words
 
-    const bool wide = (reinterpret_cast<uintptr_t>(a.iq) & 15u) == 0 && (((a.out_abs0 - a.src_abs0) & 1) == 0);   // (uniform)
+    constexpr unsigned BPS = FMT == AM_FMT_CF32 ? 8u : 2u * (unsigned)unp_fmt<FMT>::CS;     // bytes per sample
+    // (uniform) a pair of samples is one aligned load: 16 bytes of float32, 2 BPS of a raw format
+    const bool wide = (reinterpret_cast<uintptr_t>(a.iq) & (FMT == AM_FMT_CF32 ? 15u : 2u * BPS - 1u)) == 0 && (((a.out_abs0 - a.src_abs0) & 1) == 0);
     const float2 *iq2 = reinterpret_cast<const float2 *>(a.iq);
 
     for (uint32_t wa = pb; wa < pe; wa += RS_WIN) {            // windows of the share (one, unless the segments are very long)
@@ -431,7 +437,8 @@ __global__ void __launch_bounds__(RS_NT, RS_WPS) am_k_refine_seg(am_rseg_args a)
             __builtin_amdgcn_wave_barrier();
             if (G.inside) {
                 const long long Alo = A0 + ((long long)G.ga - 1) * SPC;
-                unsigned long long gbase = reinterpret_cast<unsigned long long>(iq2 + (Alo - a.src_abs0));
+                unsigned long long gbase = FMT == AM_FMT_CF32 ? reinterpret_cast<unsigned long long>(iq2 + (Alo - a.src_abs0))
+                                                              : reinterpret_cast<unsigned long long>(reinterpret_cast<const unsigned char *>(a.iq) + (Alo - a.src_abs0) * (long long)BPS);
                 gbase = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(gbase >> 32)) << 32) |
                         (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)gbase);
                 const int np = B.nrow * 16;
@@ -440,8 +447,15 @@ __global__ void __launch_bounds__(RS_NT, RS_WPS) am_k_refine_seg(am_rseg_args a)
                 for (int r = 0; r < RS_MAXR; ++r) {
                     const int p = lane + AM_WAVE * r;
                     const int pc = p < np ? p : 0;
-                    const unsigned off = ((unsigned)RC[pc >> 4] - G.ga) * (unsigned)(SPC * 8) + (unsigned)(pc & 15) * 16u;
-                    B.v[r] = fes_gload16_cached_at(gbase, off);
+                    if constexpr (FMT == AM_FMT_CF32) {
+                        const unsigned off = ((unsigned)RC[pc >> 4] - G.ga) * (unsigned)(SPC * 8) + (unsigned)(pc & 15) * 16u;
+                        B.v[r] = fes_gload16_cached_at(gbase, off);
+                    } else {
+                        // (the pair's bits wait in the piece's first two words)
+                        const unsigned off = ((unsigned)RC[pc >> 4] - G.ga) * ((unsigned)SPC * BPS) + (unsigned)(pc & 15) * (2u * BPS);
+                        const raw_pair_bits b = raw_pair_load<FMT>(reinterpret_cast<const void *>(gbase + (unsigned long long)off), 0);
+                        B.v[r].x = __uint_as_float(b.lo); B.v[r].y = __uint_as_float(b.hi);
+                    }
                 }
             }
         };
@@ -460,11 +474,17 @@ __global__ void __launch_bounds__(RS_NT, RS_WPS) am_k_refine_seg(am_rseg_args a)
                 for (int r = 0; r < RS_MAXR; ++r) {
                     const int p = lane + AM_WAVE * r;
                     if (p < np) {
-                        const fes_f2 q0 = fes_pk_mul(fes_mk2(B.v[r].x, B.v[r].y), fes_mk2(B.v[r].x, B.v[r].y));
-                        const fes_f2 q1 = fes_pk_mul(fes_mk2(B.v[r].z, B.v[r].w), fes_mk2(B.v[r].z, B.v[r].w));
                         float2 mm;
-                        mm.x = q0.x + q0.y;                           // a1: fl(fl(I*I) + fl(Q*Q))
-                        mm.y = q1.x + q1.y;
+                        if constexpr (FMT == AM_FMT_CF32) {
+                            const fes_f2 q0 = fes_pk_mul(fes_mk2(B.v[r].x, B.v[r].y), fes_mk2(B.v[r].x, B.v[r].y));
+                            const fes_f2 q1 = fes_pk_mul(fes_mk2(B.v[r].z, B.v[r].w), fes_mk2(B.v[r].z, B.v[r].w));
+                            mm.x = q0.x + q0.y;                           // a1: fl(fl(I*I) + fl(Q*Q))
+                            mm.y = q1.x + q1.y;
+                        } else {
+                            raw_pair_bits b;
+                            b.lo = __float_as_uint(B.v[r].x); b.hi = __float_as_uint(B.v[r].y);
+                            mm = raw_pair_mag2<FMT>(b);
+                        }
                         const int s = p >> 4;
                         float *row = (s < B.cnt) ? XMw + s * RS_XS : XEw + (s - B.cnt) * RS_XS;
                         *reinterpret_cast<float2 *>(row + 2 * (p & 15)) = mm;
@@ -476,14 +496,20 @@ __global__ void __launch_bounds__(RS_NT, RS_WPS) am_k_refine_seg(am_rseg_args a)
                 for (int p = lane; p < np; p += AM_WAVE) {
                     const int s = p >> 4;
                     const long long aa = A0 + ((long long)RC[s] - 1) * SPC + 2 * (p & 15);
-                    float2 u0, u1;
-                    u0.x = 0.0f; u0.y = 0.0f; u1 = u0;
-                    if (aa >= a.src_abs0 && aa < a.src_abs1) u0 = iq2[aa - a.src_abs0];
-                    if (aa + 1 >= a.src_abs0 && aa + 1 < a.src_abs1) u1 = iq2[aa + 1 - a.src_abs0];
-                    const float r0 = u0.x * u0.x, i0 = u0.y * u0.y, r1 = u1.x * u1.x, i1 = u1.y * u1.y;
                     float2 mm;
-                    mm.x = r0 + i0;
-                    mm.y = r1 + i1;
+                    if constexpr (FMT == AM_FMT_CF32) {
+                        float2 u0, u1;
+                        u0.x = 0.0f; u0.y = 0.0f; u1 = u0;
+                        if (aa >= a.src_abs0 && aa < a.src_abs1) u0 = iq2[aa - a.src_abs0];
+                        if (aa + 1 >= a.src_abs0 && aa + 1 < a.src_abs1) u1 = iq2[aa + 1 - a.src_abs0];
+                        const float r0 = u0.x * u0.x, i0 = u0.y * u0.y, r1 = u1.x * u1.x, i1 = u1.y * u1.y;
+                        mm.x = r0 + i0;
+                        mm.y = r1 + i1;
+                    } else {
+                        mm.x = 0.0f; mm.y = 0.0f;
+                        if (aa >= a.src_abs0 && aa < a.src_abs1) mm.x = raw_mag2_at<FMT>(a.iq, aa - a.src_abs0);
+                        if (aa + 1 >= a.src_abs0 && aa + 1 < a.src_abs1) mm.y = raw_mag2_at<FMT>(a.iq, aa + 1 - a.src_abs0);
+                    }
                     float *row = (s < B.cnt) ? XMw + s * RS_XS : XEw + (s - B.cnt) * RS_XS;
                     *reinterpret_cast<float2 *>(row + 2 * (p & 15)) = mm;
                 }
@@ -757,7 +783,7 @@ hipError_t am_launch_refine_seg(const am_fe_marks &m, const am_fe_layout &l, con
     if (!l.alike() && l.words_short() == 0) return hipErrorInvalidValue;   // (levelled: the short segments have a step too)
     am_rseg_args a;
     a.bits = m.bits; a.wg_cnt = m.wg_cnt; a.wg_max = m.wg_max; a.nwg = nwg; a.words_per_wg = words_per_wg; a.nwords = l.nwords(); a.Mcap = r.M;
-    a.vspan = l.vspan(); a.nv = l.nv(); a.end_j = in.end_j; a.iq = rows.iq; a.src_abs0 = rows.src_abs0; a.src_abs1 = rows.src_abs1;
+    a.vspan = l.vspan(); a.nv = l.nv(); a.end_j = in.end_j; a.iq = static_cast<const float *>(rows.iq); a.src_abs0 = rows.src_abs0; a.src_abs1 = rows.src_abs1;
     a.out_abs0 = rows.out_abs0; a.avg_sparse = in.avg; a.s1 = rows.s1; a.thr_lin = in.thr_lin; a.pos = r.pos; a.e = r.e; a.tgt = r.tgt;
     a.jump0 = r.jump0; a.total_out = total_out; a.inavg = r.inavg; a.valid = r.valid;
     // levelled segments: the first n_long of words_per_wg words, the others one step shorter
@@ -775,8 +801,19 @@ hipError_t am_launch_refine_seg(const am_fe_marks &m, const am_fe_layout &l, con
     if (hipMalloc(reinterpret_cast<void **>(&a.prof), (size_t)grid * 12 * sizeof(long long)) != hipSuccess) a.prof = nullptr;
     if (a.prof) (void)hipMemsetAsync(a.prof, 0, (size_t)grid * 12 * sizeof(long long), s);
 #endif
-    if (rows.use_pmf) hipLaunchKernelGGL(am_k_refine_seg<true>, dim3(grid), dim3(RS_NT), 0, s, a);
-    else hipLaunchKernelGGL(am_k_refine_seg<false>, dim3(grid), dim3(RS_NT), 0, s, a);
+    switch (rows.fmt) {
+#define RS_LAUNCH(F) \
+    case F: \
+        if (rows.use_pmf) hipLaunchKernelGGL((am_k_refine_seg<true, F>), dim3(grid), dim3(RS_NT), 0, s, a); \
+        else hipLaunchKernelGGL((am_k_refine_seg<false, F>), dim3(grid), dim3(RS_NT), 0, s, a); \
+        break;
+    RS_LAUNCH(AM_FMT_CF32)
+    RS_LAUNCH(AM_FMT_SC16)
+    RS_LAUNCH(AM_FMT_CS8)
+    RS_LAUNCH(AM_FMT_CU8)
+#undef RS_LAUNCH
+    default: return hipErrorInvalidValue;
+    }
     const hipError_t lrc = hipGetLastError();
 #if defined(RS_PROFILE)
     if (a.prof) {

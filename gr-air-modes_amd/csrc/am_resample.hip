@@ -18,6 +18,7 @@
 // Also in this file, the other input-side stages: am_k_unpack (native sample formats sc16 / cs8 / cu8 -> float32, the
 // definition is air_modes/formats.py) and the pinned uploader of a host source.
 #include "am_internal.h"
+#include "am_raw_iq.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -216,27 +217,14 @@ int am_resampler_work(am_resampler *h, const float *iq, uint64_t n, uint32_t fla
 
 /* ---- native sample formats: raw integer I,Q -> float32 I,Q (python/radio.py:164-231) -----------------------------
  * The reference's sources convert on the host before rx_path sees a sample (uhd cpu_format="fc32", osmosdr.source); here the
- * raw bytes cross PCIe and the widening runs on the device, in front of the front end.  DEFINITION: air_modes/formats.py
- *
- *   sc16  float(x) * 2^-15        cs8  float(x) * 2^-7        cu8  (float(x) - 127.5f) * 2^-7
- *
- * Every operation is exact in float32 (|x| < 2^16; x - 127.5 has 9 significant bits; a power-of-two scale), so forms that
- * are equal over the reals are equal bit for bit, and the kernel picks the cheapest:
- *   cu8   v_cvt_f32_ubyteN, then ONE fma: u * 2^-7 - 127.5 * 2^-7 (the exact value is representable, so the single rounding
- *         of the fma returns it)
- *   cs8   x + 128 = the byte with its top bit flipped, read as unsigned: one v_xor per FOUR components, then the cu8 pair
- *         with -1.0 as the addend
- *   sc16  sign-extending extract, v_cvt_f32_i32, one multiply
+ * raw bytes cross PCIe and the widening runs on the device: in this kernel, in front of the front end, or -- at 64 Msps -- inside the
+ * kernels that read the samples (am_k_fe3<FMT> and what follows it).  The conversion itself, word by word and component by
+ * component (unp_word<FMT>, unp_one<FMT>), is am_raw_iq.h's, shared with those kernels.
  * A stream of COMPONENTS, not of samples: the raw pointer is aligned to its component only, so the 16-byte body may begin
  * in the middle of a sample.  Body: 16-byte loads aligned on the RAW side (nt: every raw byte is read once), 16-byte stores at
  * the 4-byte alignment that leaves (plain policy: the front end reads the floats next, and a chunk fits the Infinity Cache).
  * Head and tail (fewer than 16 components each) go one component per thread.  Nothing outside [raw, raw + nc * CS) is read,
  * nothing outside [out, out + nc) written. */
-template <int FMT> struct unp_fmt;
-template <> struct unp_fmt<AM_FMT_SC16> { static constexpr int CS = 2; };
-template <> struct unp_fmt<AM_FMT_CS8> { static constexpr int CS = 1; };
-template <> struct unp_fmt<AM_FMT_CU8> { static constexpr int CS = 1; };
-
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef unsigned int unp_u4 __attribute__((ext_vector_type(4)));
 typedef float unp_f4a __attribute__((ext_vector_type(4), aligned(4)));
@@ -263,30 +251,6 @@ __device__ __forceinline__ void unp_store16(float *p, const float *f)        // 
 #else
     memcpy(p, f, 16);
 #endif
-}
-
-// one component, the definition as written (head and tail)
-template <int FMT>
-__device__ __forceinline__ float unp_one(const unsigned char *p)
-{
-    if (FMT == AM_FMT_SC16) return (float)(int)*reinterpret_cast<const int16_t *>(p) * 0x1p-15f;
-    if (FMT == AM_FMT_CS8) return (float)(int)*reinterpret_cast<const signed char *>(p) * 0x1p-7f;
-    return ((float)(int)*p - 127.5f) * 0x1p-7f;
-}
-
-// the 16 / CS components of one 32-bit word
-template <int FMT>
-__device__ __forceinline__ void unp_word(uint32_t w, float *f)
-{
-    if (FMT == AM_FMT_SC16) {
-        f[0] = (float)(int)(int16_t)(w & 0xffffu) * 0x1p-15f;
-        f[1] = (float)((int32_t)w >> 16) * 0x1p-15f;
-    } else {
-        const float c = FMT == AM_FMT_CS8 ? -1.0f : -127.5f * 0x1p-7f;
-        if (FMT == AM_FMT_CS8) w ^= 0x80808080u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f[k] = fmaf((float)((w >> (8 * k)) & 0xffu), 0x1p-7f, c);
-    }
 }
 
 // value of `v` in lane j of the caller's group of four lanes (DPP quad_perm:[j,j,j,j])

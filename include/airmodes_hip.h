@@ -631,9 +631,26 @@ AM_API int am_synchronize(am_ctx *ctx);
 /* am_process_iq on am_unpack's output (rx_path behind python/radio.py:164-231's sources): same flags, same chunking
  * rules, same results.  Host input: the RAW bytes are copied to a staging buffer of the context and unpacked straight
  * behind the carried tail, so a sample crosses PCIe once, at its raw width.  AM_FMT_CF32 is am_process_iq itself.
+ * (At 64 Msps nothing is unpacked: the kernels of the scan read the raw samples themselves and the carried tail stays at raw
+ * width -- DESIGN.md 12; the packets are the same by definition, and nothing here changes for the caller.)
  * AM_EINVAL for an unknown format or a null pointer with n_complex > 0. */
 AM_API int am_process_samples(am_ctx *ctx, const void *raw, uint64_t n_complex, int fmt, uint32_t flags,
                               am_packet *out, uint64_t cap, uint64_t *n_out);
+
+/* The raw front end: a switch and a diagnostic for tests and measurement, not part of the drop-in surface
+ * (they stand in this header because the list of airmodes_hip_debug.h is pinned by tests/test_capi_host.py).
+ * At 64 Msps a stream of AM_FMT_SC16 / CS8 / CU8 samples (am_process_samples) is scanned as it is: am_k_fe3<FMT>,
+ * am_k_refine_seg<PMF, FMT> and am_k_extract_slice_iq<32, ..., 1> read the integers, the carried tail stays at raw width and
+ * am_k_unpack does not run.  Packets are the same either way (they are DEFINED as those of the converted stream).  The
+ * switch is the A/B lever, not a user option: default 1; it survives am_reset and am_set_rate; a new value takes effect when
+ * the next stream starts (after am_create, am_reset, am_set_rate or AM_F_FLUSH).  Every other configuration -- other rates,
+ * the DC blocker, am_submit_iq, pipes, K streams, shards -- widens first, whatever the switch says; so does the rest of a
+ * stream whose calls change format. */
+AM_API int am_set_raw_front_end(am_ctx *ctx, int on);
+AM_API int am_get_raw_front_end(const am_ctx *ctx);
+/* Diagnostic: the AM_FMT_* the front end of the last scan read -- AM_FMT_CF32 for float32 input and for a raw stream that was
+ * widened first (also before any scan); negative on a null context. */
+AM_API int am_last_scan_format(const am_ctx *ctx);
 
 /* last error text of the context (or of am_create when ctx == NULL) */
 AM_API const char *am_last_error(const am_ctx *ctx);

@@ -12,7 +12,12 @@ address gate was: `am_k_extract_slice_iq<32, 1, 0>` is matched with `am_k_extrac
     python tools/isa_compare.py --same-names parent.s this.s
 is for a commit that adds a VALUE of an existing template argument instead (GATE = 2 for am_set_address_repair): every kernel
 whose name contains "slice" or "gate" and which the first listing has under the same name is compared with that one; the others
-are listed as new."""
+are listed as new.
+
+    python tools/isa_compare.py --pattern 'am_k_fe3|am_k_refine_seg' parent.s this.s
+chooses the kernels by a regular expression on the mangled name instead of "slice" (either mode; listings of other files than
+am_kernels.hip are made the same way).  The template arguments in front of the new last one may be numbers or true / false
+(`am_k_refine_seg<true, 0>` is matched with `am_k_refine_seg<true>`, `am_k_fe3<0>` with `am_k_fe3`)."""
 import re
 import subprocess
 import sys
@@ -46,8 +51,8 @@ def demangle(names):
     return {n: d.split("(")[0].replace("void ", "") for n, d in zip(names, res)}
 
 
-def same_names(a, b):
-    na, nb = demangle([k for k in a]), demangle([k for k in b if "slice" in k or "gate" in k])
+def same_names(a, b, wanted):
+    na, nb = demangle([k for k in a]), demangle([k for k in b if wanted(k)])
     first = {d: k for k, d in na.items()}
     worst = 0
     for k, d in sorted(nb.items(), key=lambda kv: kv[1]):
@@ -64,16 +69,23 @@ def same_names(a, b):
 
 
 def main():
-    if sys.argv[1] == "--same-names":
-        same_names(kernels(sys.argv[2]), kernels(sys.argv[3]))
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-    na, nb = demangle([k for k in a if "slice" in k]), demangle([k for k in b if "slice" in k])
+    args = sys.argv[1:]
+    pattern = None
+    if "--pattern" in args:
+        at = args.index("--pattern")
+        pattern = re.compile(args[at + 1])
+        del args[at:at + 2]
+    if args[0] == "--same-names":
+        same_names(kernels(args[1]), kernels(args[2]), (lambda k: pattern.search(k)) if pattern else (lambda k: "slice" in k or "gate" in k))
+    wanted = (lambda k: pattern.search(k)) if pattern else (lambda k: "slice" in k)
+    a, b = kernels(args[0]), kernels(args[1])
+    na, nb = demangle([k for k in a if wanted(k)]), demangle([k for k in b if wanted(k)])
     first = {d: k for k, d in na.items()}
     worst = 0
     for k, d in sorted(nb.items(), key=lambda kv: kv[1]):
         lines, info = b[k]
         text = "%-36s %5d lines  %s" % (d, len(lines), " ".join("%s=%s" % kv for kv in info.items()))
-        m = re.match(r"(\w+)<((?:\d+, )*)0>$", d)
+        m = re.match(r"(\w+)<((?:\w+, )*)0>$", d)
         if m:
             old = m.group(1) + ("<%s>" % m.group(2)[:-2] if m.group(2) else "")
             same = old in first and a[first[old]][0] == lines and a[first[old]][1] == info

@@ -460,11 +460,16 @@ class Context(_DecodeOptions, _DecodeStats):
 
     def set_raw_front_end(self, on):
         """Diagnostic switch (default on): at 64 Msps a raw stream is scanned as it is, without the float copy.  Takes effect
-        when the next stream starts."""
-        self._chk(self.lib.L.am_set_raw_front_end(self._h, 1 if on else 0))
+        when the next stream starts.  2 (not True): also at 2, 4, 8, 10, 16, 20, 32 and 40 Msps (opt-in)."""
+        level = 2 if on == 2 else (1 if on else 0)                   # (True == 1: True and False keep meaning 1 and 0)
+        self._chk(self.lib.L.am_set_raw_front_end(self._h, level))
 
     def get_raw_front_end(self):
         return bool(self.lib.L.am_get_raw_front_end(self._h))
+
+    def raw_front_end_level(self):
+        """The stored level: 0 = widen first everywhere, 1 = native at 64 Msps (default), 2 = native at every specialised rate."""
+        return int(self.lib.L.am_get_raw_front_end(self._h))
 
     def last_scan_format(self):
         """formats.code of what the last scan's front end read: that of the input on the raw route, else 0 (float32)."""

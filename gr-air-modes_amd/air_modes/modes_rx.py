@@ -70,6 +70,10 @@ def build_parser():
                     help="slice these downlink formats (18: non-transponder extended squitter, 19: military extended "
                     "squitter) as 112 bits and check their parity, instead of cutting them to 56 bits as "
                     "slicer_impl.cc:140 does [default: none]")
+    ap.add_argument("--raw-front-end", type=int, choices=[0, 1, 2], default=None,
+                    help="sc16 / cs8 / cu8 input scanned as it is, without the float32 copy: 0 = never, 1 = at 64 Msps, "
+                    "2 = at 2, 4, 8, 10, 16, 20, 32, 40 and 64 Msps (input below 4 Msps is resampled as float32 first "
+                    "unless --no-resample) [default: the library's, 1]")
     ap.add_argument("-l", "--location", default=None, help="receiver position as lat,lon (enables range/bearing "
                     "and surface positions)")                                                            # modes_rx:40
     ap.add_argument("-n", "--no-print", action="store_true", help="do not print decoded reports")       # modes_rx:45
@@ -102,7 +106,8 @@ def main(argv=None, out=None):
         rx_rate, resampler = 4e6, resample.gpu_resampler(4e6 / args.rate)
     rx = rx_path(rx_rate, args.threshold, queue, use_pmf=args.pmf, use_dcblock=args.dcblock, fix_errors=args.fix_errors,
                  address_gate=args.address_gate, address_ttl=args.address_ttl,
-                 address_repair=args.address_repair, long_formats=args.long_formats)    # (below 4 Msps: the window runs at 4 Msps too)
+                 address_repair=args.address_repair, long_formats=args.long_formats,
+                 raw_front_end=args.raw_front_end)                   # (below 4 Msps: the window runs at 4 Msps too)
     publisher = pubsub()
     feed = make_parser(publisher, long_formats=args.long_formats)
     my_position = [float(n) for n in args.location.split(",")] if args.location else None

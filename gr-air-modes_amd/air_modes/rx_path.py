@@ -14,7 +14,9 @@ from .blocks import slicer as _slicer
 
 class rx_path(object):
     def __init__(self, rate, threshold, queue, use_pmf=False, use_dcblock=False, device=-1, lib=None, fix_errors=0,
-                 address_gate=0, address_ttl=60.0, address_repair=0, long_formats=0):
+                 address_gate=0, address_ttl=60.0, address_repair=0, long_formats=0, raw_front_end=None):
+        """raw_front_end: None leaves the library's default; 0, 1 or 2 sets the level (Context.set_raw_front_end: 2 = sc16 /
+        cs8 / cu8 input is scanned as it is at 2 .. 40 Msps too, not only at 64)."""
         self._rate = int(rate)
         self._threshold = threshold
         self._queue = queue
@@ -30,6 +32,10 @@ class rx_path(object):
         self.samples = 0
         # (through this object's own setters: set_address_gate notes that `gated` has to be kept)
         _capi.apply_decode_options(self, fix_errors, address_gate, address_ttl, address_repair, long_formats)
+        if raw_front_end is not None:
+            if raw_front_end not in (0, 1, 2):
+                raise ValueError("raw_front_end: None, 0, 1 or 2")
+            self._ctx.set_raw_front_end(int(raw_front_end))
 
     # --- reference surface: python/rx_path.py:67-87 ---
     def set_rate(self, rate):

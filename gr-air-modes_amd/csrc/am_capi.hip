@@ -554,7 +554,8 @@ int run_frontend(am_ctx *c, const float *src, uint64_t src_abs0, uint64_t src_ab
 
 // A raw stream can be scanned as it is where the scan runs am_k_fe3 and am_k_refine_seg (64 Msps, product configuration) on the
 // samples themselves: no DC blocker in front.  (The row loader of am_k_gather_wg -- fused_refine off, test builds -- reads float32.)
-static bool native_front_end(const am_ctx *c);
+// level (am_set_raw_front_end): AM_RAW_FE_ALL adds the rates am_k_fe4 serves, 2 .. 40 Msps.
+static bool native_front_end(const am_ctx *c, int level);
 
 // Which kernels a scan of this context runs.  PATH_TILE exists in TEST builds only (-DAM_WITH_TILE_KERNEL: tests/gpu_variants,
 // tests/emu; round 5: the product library no longer carries am_k_fe2 nor the split refinement behind it).
@@ -569,9 +570,12 @@ static ScanPath scan_path(const am_ctx *c, bool dense_wanted)
     return PATH_GENERIC;
 }
 
-static bool native_front_end(const am_ctx *c)
+static bool native_front_end(const am_ctx *c, int level)
 {
-    return scan_path(c, false) == PATH_STREAM && am_fe4_uses_fe3(c->spc) && c->fused_refine && !c->use_dcblock;
+    if (scan_path(c, false) != PATH_STREAM || c->use_dcblock) return false;
+    if (am_fe4_uses_fe3(c->spc) && c->fused_refine) return level >= AM_RAW_FE_64;
+    // 2 .. 40 Msps: am_k_fe4<..., FMT> stages the samples, the refinement reads the rows it wrote, the extraction reads the samples
+    return level >= AM_RAW_FE_ALL && am_fe4_reads_raw(c->spc) != 0;
 }
 
 // A scan starts: whatever the one before left for its tail is gone (which front end ran last stays on record until one runs again)
@@ -703,7 +707,8 @@ int run_front_and_candidates(am_ctx *c, const void *vsrc, uint64_t src_abs0, uin
                              int fmt = AM_FMT_CF32)
 {
     const ScanPath path = scan_path(c, avg != nullptr);
-    if (fmt != AM_FMT_CF32 && !(path == PATH_STREAM && native_front_end(c)))
+    // (the stream's level was read when it started, and the switch may have moved since: whether kernels for raw samples exist)
+    if (fmt != AM_FMT_CF32 && !(path == PATH_STREAM && native_front_end(c, AM_RAW_FE_ALL)))
         return fail(c, AM_EINVAL, "internal: no kernel reads raw samples on this path");
     const float *src = static_cast<const float *>(vsrc);      // (what the float32-only kernels below are handed)
     HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
@@ -1519,7 +1524,7 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
     // keeps them raw: view, carried tail and scan are of the input's format.  Every other stream is float32 (the staged form).  A
     // native stream whose format changes goes on staged from this call: the carried tail is widened once.
     if (c->total_in == 0 && c->carry_n == 0)
-        c->view_fmt = (fmt != AM_FMT_CF32 && c->raw_fe && !submit && native_front_end(c)) ? fmt : AM_FMT_CF32;
+        c->view_fmt = (fmt != AM_FMT_CF32 && !submit && native_front_end(c, c->raw_fe)) ? fmt : AM_FMT_CF32;
     else if (c->view_fmt != AM_FMT_CF32 && fmt != c->view_fmt) {
         if (c->carry_n) {
             ENSURE(c, c->carry2, c->carry_n * 2 * sizeof(float));
@@ -1637,7 +1642,11 @@ static int process_iq_core(am_ctx *c, const void *in, uint64_t n, int fmt, uint3
     } else {
         const uint64_t blk = (c->next_pos / L) * L;
         const uint64_t hist = LH + (c->use_dcblock ? am_dcblock_history(c->spc) : 0);
-        const uint64_t C0 = blk > hist ? blk - hist : 0;
+        uint64_t C0 = blk > hist ? blk - hist : 0;
+        // the native route: the next view starts on a multiple of 8 samples (16 bytes of cs8 / cu8).  A block is a multiple of 8
+        // samples at every rate, so every step of am_k_fe4<..., FMT> then starts on a 16-byte boundary of the view and every pair load
+        // is aligned; the up to 7 samples more are history no scan looks at.  (64 Msps: blk - hist is such a multiple already.)
+        if (vfmt != AM_FMT_CF32) C0 &= ~(uint64_t)7;
         const uint64_t keep = S1 - C0;
         if (keep) {
             ENSURE(c, c->carry2, keep * vb);
@@ -3155,7 +3164,9 @@ int am_last_frontend(const am_ctx *c) { return c ? (int)c->scan.path : AM_EINVAL
 int am_set_raw_front_end(am_ctx *c, int on)
 {
     if (!c) return AM_EINVAL;
-    c->raw_fe = on ? 1 : 0;                                 // (read when the next stream starts: process_iq_core)
+    // AM_RAW_FE_OFF / _64 / _ALL; every other non-zero value means 1, as before the levels (read when the next stream starts:
+    // process_iq_core)
+    c->raw_fe = on == AM_RAW_FE_ALL ? AM_RAW_FE_ALL : (on ? AM_RAW_FE_64 : AM_RAW_FE_OFF);
     return AM_OK;
 }
 int am_get_raw_front_end(const am_ctx *c) { return c ? c->raw_fe : 0; }

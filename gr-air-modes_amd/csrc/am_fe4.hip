@@ -1,8 +1,9 @@
 // am_fe4.hip -- the streaming fused front end + first-stage preamble detection for gfx950, every rate the library
 // specialises: 2, 4, 8, 10, 16, 20, 32, 40 and 64 Msps (the rate BASELINE.json's metric is quoted on).
 //
-// One template, am_k_fe4<SPC, G, NW>: SPC samples per chip, a lane owns a UNIT of G consecutive chips (R = G * SPC samples
-// in registers, even: 32 at 64 Msps with G = 1, 30 at 20 and 10 Msps, 24 at 2 Msps), NW waves per workgroup.
+// One template, am_k_fe4<SPC, G, NW, FMT>: SPC samples per chip, a lane owns a UNIT of G consecutive chips (R = G * SPC samples
+// in registers, even: 32 at 64 Msps with G = 1, 30 at 20 and 10 Msps, 24 at 2 Msps), NW waves per workgroup, samples of format
+// FMT (float32, or sc16 / cs8 / cu8 as a radio delivers them: only the staging differs).
 //
 //   * PERSISTENT workgroups: a workgroup owns a contiguous segment of the stream and walks it in steps of US units.
 //     What a step needs from the past -- the pulse-matched power bb of the last LAGU + 48 chips' worth of units and
@@ -39,6 +40,7 @@
 //
 // Reference: python/rx_path.py:35-54 (spc = rate / 2e6, |.|^2, moving averages), lib/preamble_impl.cc:172-179 (test).
 #include "am_fe_stream.h"
+#include "am_raw_iq.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -198,10 +200,24 @@ __device__ __forceinline__ void fe4_put_piece(const fe4_smem<SPC, G, NW> &L, int
         if (k + 1 >= 0 && k + 1 < SPC) d[k + 1] = m1;
     }
 }
-template <int SPC, int G, int NW>
+template <int SPC, int G, int NW, int FMT = AM_FMT_CF32>
 __device__ __forceinline__ void fe4_stage_guarded(const am_fe4_args &a, const fe4_smem<SPC, G, NW> &L, long long A0, int slot0, int tid)
 {
     using C = fe4_cfg<SPC, G, NW>;
+    if constexpr (FMT != AM_FMT_CF32) {
+        // raw samples of format FMT (am_raw_iq.h): the same pieces, |.|^2 of the float32 pair am_k_unpack would have written
+#pragma unroll 1
+        for (int j = 0; j < C::NLD; ++j) {
+            const int p = tid + C::NT * j;
+            if (p >= C::PIECES) break;
+            const long long n = A0 + 2 * (long long)p;
+            float m0 = 0.0f, m1 = 0.0f;
+            if (n >= a.src_abs0 && n < a.src_abs1) m0 = raw_mag2_at<FMT>(a.iq, n - a.src_abs0);
+            if (n + 1 >= a.src_abs0 && n + 1 < a.src_abs1) m1 = raw_mag2_at<FMT>(a.iq, n + 1 - a.src_abs0);
+            fe4_put_piece<SPC, G, NW>(L, slot0, (2 * p) / C::R, (2 * p) % C::R, m0, m1);
+        }
+        return;
+    }
     const float2 *iq2 = reinterpret_cast<const float2 *>(a.iq);
 #pragma unroll 1
     for (int j = 0; j < C::NLD; ++j) {
@@ -222,7 +238,10 @@ __device__ __forceinline__ void fe4_stage_guarded(const am_fe4_args &a, const fe
 // per piece for the ring's wrap-around, the rest is the instructions' immediate offsets.  (The division and the remainder by
 // R per piece, the 32-bit multiply by the row stride -- quarter rate -- and the select chains around them were a quarter of
 // the kernel's VALU time, which is what bounds it: DESIGN.md 5.1a.)  J0: rounds below it are not loaded (ring rebuild).
-template <int SPC, int G, int NW, int J0>
+// FMT other than AM_FMT_CF32: the same pieces of two samples in the same places, each one load of 8 bytes of sc16
+// or 4 of cs8 / cu8 (R is 20, 24, 30 or 32 samples: a wider load would straddle rows at 30 and 20); a step's first byte is 16-byte
+// aligned in every format (fes_fill_args), so every piece is aligned to a pair.
+template <int SPC, int G, int NW, int J0, int FMT = AM_FMT_CF32>
 __device__ __forceinline__ void fe4_stage_rows(const am_fe4_args &a, const fe4_smem<SPC, G, NW> &L, long long A0, int slot0, int tid)
 {
     using C = fe4_cfg<SPC, G, NW>;
@@ -233,6 +252,39 @@ __device__ __forceinline__ void fe4_stage_rows(const am_fe4_args &a, const fe4_s
     const int sc = slot0 + c0;
     float *const row = L.X + fes_mul24(sc, C::RS) + 2 * k;            // round 0's destination
     float *const roww = row - C::CRU * C::RS;
+    if constexpr (FMT != AM_FMT_CF32) {
+        constexpr unsigned PB = 4u * unp_fmt<FMT>::CS;                // bytes per piece
+        const unsigned long long gb = reinterpret_cast<unsigned long long>(a.iq) + (unsigned long long)(A0 - a.src_abs0) * (PB / 2u);
+        raw_pair_bits v[ROUNDS];
+#pragma unroll
+        for (int j = J0; j < ROUNDS; ++j) {
+            if (UPR * (j + 1) > C::US && c0 + UPR * j >= C::US) continue; // (the last round may be short)
+            unsigned long long g = gb + (unsigned long long)j * (USED * PB);
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm("" : "+s"(g));                                        // (scalar base per round + the lane's offset)
+#endif
+            v[j] = raw_pair_load<FMT>(reinterpret_cast<const void *>(g), (long long)(unsigned)tid);
+        }
+#pragma unroll
+        for (int j = J0; j < ROUNDS; ++j) {
+            if (UPR * (j + 1) > C::US && c0 + UPR * j >= C::US) continue;
+            const float2 mm = raw_pair_mag2<FMT>(v[j]);
+            float *dst = (sc >= C::CRU - UPR * j) ? roww : row;
+            *reinterpret_cast<float2 *>(dst + j * (UPR * C::RS)) = mm;
+#pragma unroll
+            for (int m = 1; m < NW; ++m) {
+                constexpr int LUc = C::LU;
+                const int cstar = LUc * m - 1 - UPR * j;              // (compile time after unrolling)
+                if (cstar >= 0 && cstar < UPR && c0 == cstar && 2 * k >= C::R - SPC - (SPC & 1)) {
+                    float *d = L.MLW + (m - 1) * SPC;
+                    const int kk = 2 * k - (C::R - SPC);
+                    if (kk >= 0) d[kk] = mm.x;
+                    if (kk + 1 >= 0 && kk + 1 < SPC) d[kk + 1] = mm.y;
+                }
+            }
+        }
+        return;
+    }
     const unsigned long long gb = reinterpret_cast<unsigned long long>(a.iq) + (unsigned long long)(A0 - a.src_abs0) * 8ull;
     const unsigned off = (unsigned)tid * 16u;
     float4 v[ROUNDS];
@@ -749,7 +801,9 @@ __device__ __forceinline__ void fe4_step(const am_fe4_args &a, const fe4_smem<SP
     }
 }
 
-template <int SPC, int G, int NW>
+// FMT: the format of the samples at a.iq.  Only the staging in front of barrier B1 differs; am_k_fe4<SPC, G, NW, AM_FMT_CF32> is the
+// kernel as it was before the other formats (profiles/raw_rates/isa_cf32_kernels.txt).
+template <int SPC, int G, int NW, int FMT = AM_FMT_CF32>
 __global__ void __launch_bounds__(AM_WAVE * NW, (fe4_cfg<SPC, G, NW>::MINW)) am_k_fe4(am_fe4_args a)
 {
     using C = fe4_cfg<SPC, G, NW>;
@@ -787,10 +841,10 @@ __global__ void __launch_bounds__(AM_WAVE * NW, (fe4_cfg<SPC, G, NW>::MINW)) am_
         fes_step_priority((unsigned)(step - sb + 1));                   // (am_fe_stream.h: the CU's workgroups end together)
         FE4_STAMP(4);
         if (have) {
-            if (test) fe4_stage_rows<SPC, G, NW, 0>(a, L, a.out_abs0 + (long long)step * C::T, slot0, tid);
-            else fe4_stage_rows<SPC, G, NW, WARM_J0>(a, L, a.out_abs0 + (long long)step * C::T, slot0, tid);
+            if (test) fe4_stage_rows<SPC, G, NW, 0, FMT>(a, L, a.out_abs0 + (long long)step * C::T, slot0, tid);
+            else fe4_stage_rows<SPC, G, NW, WARM_J0, FMT>(a, L, a.out_abs0 + (long long)step * C::T, slot0, tid);
         } else
-            fe4_stage_guarded<SPC, G, NW>(a, L, a.out_abs0 + (long long)step * C::T, slot0, tid);
+            fe4_stage_guarded<SPC, G, NW, FMT>(a, L, a.out_abs0 + (long long)step * C::T, slot0, tid);
         FE4_STAMP(5);
         fes_barrier();                                                // B1: |.|^2 of this step staged
         FE4_STAMP(0);
@@ -900,7 +954,7 @@ am_fe_layout am_fe_plan(int spc, long long out_n, unsigned resident, bool levell
     return l;
 }
 
-template <int SPC, int G, int NW>
+template <int SPC, int G, int NW, int FMT = AM_FMT_CF32>
 static hipError_t fe4_launch(const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu)
 {
     using C = fe4_cfg<SPC, G, NW>;
@@ -912,11 +966,11 @@ static hipError_t fe4_launch(const am_fe_stream_req &r, am_fe_layout *layout, hi
     (void)hipGetDevice(&dev);
     int wpc = (dev >= 0 && dev < 64) ? per_cu[dev].load(std::memory_order_acquire) : 0;
     if (wpc <= 0) {
-        hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&am_k_fe4<SPC, G, NW>),
+        hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void *>(&am_k_fe4<SPC, G, NW, FMT>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (rc != hipSuccess) return rc;
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(&am_k_fe4<SPC, G, NW>), C::NT, lds) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(&am_k_fe4<SPC, G, NW, FMT>), C::NT, lds) != hipSuccess ||
             nb <= 0)
             nb = FE4_WG_PER_CU;
         wpc = nb > 8 ? 8 : nb;
@@ -939,7 +993,7 @@ static hipError_t fe4_launch(const am_fe_stream_req &r, am_fe_layout *layout, hi
     // blocking; prints mean cycles per step and phase -- never in the default build
     if (hipMalloc(reinterpret_cast<void **>(&a.prof), (size_t)grid * NW * 8 * sizeof(long long)) != hipSuccess) a.prof = nullptr;
 #endif
-    hipLaunchKernelGGL((am_k_fe4<SPC, G, NW>), dim3(grid), dim3(C::NT), lds, s, a);
+    hipLaunchKernelGGL((am_k_fe4<SPC, G, NW, FMT>), dim3(grid), dim3(C::NT), lds, s, a);
     hipError_t lrc = hipGetLastError();
 #if defined(FE4_PROFILE)
     if (a.prof) {
@@ -968,21 +1022,38 @@ static hipError_t fe4_launch(const am_fe_stream_req &r, am_fe_layout *layout, hi
     return lrc;
 }
 
+// the instantiation for the format of the request's samples
+template <int SPC, int G, int NW>
+static hipError_t fe4_launch_fmt(const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu)
+{
+    switch (r.fmt) {
+    case AM_FMT_CF32: return fe4_launch<SPC, G, NW, AM_FMT_CF32>(r, layout, s, wgs_per_cu);
+    case AM_FMT_SC16: return fe4_launch<SPC, G, NW, AM_FMT_SC16>(r, layout, s, wgs_per_cu);
+    case AM_FMT_CS8: return fe4_launch<SPC, G, NW, AM_FMT_CS8>(r, layout, s, wgs_per_cu);
+    case AM_FMT_CU8: return fe4_launch<SPC, G, NW, AM_FMT_CU8>(r, layout, s, wgs_per_cu);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// am_k_fe4 reads raw samples at the rates it serves in the product build (64 Msps: am_k_fe3<FMT>; the FE4_64MSPS tuning builds'
+// am_k_fe4<32, 1, NW> reads float32 only)
+int am_fe4_reads_raw(int spc) { return fe4_g_of(spc) != 0 && spc != 32 ? 1 : 0; }
+
 hipError_t am_launch_fe4(int spc, const am_fe_stream_req &r, am_fe_layout *layout, hipStream_t s, int wgs_per_cu, bool levelled)
 {
     if (!am_fe4_supported(spc)) return hipErrorInvalidValue;
     if (FE4_USE_FE3(spc)) return am_launch_fe3(r, layout, s, wgs_per_cu, levelled);
-    if (r.fmt != AM_FMT_CF32) return hipErrorInvalidValue;            // (am_k_fe4 reads float32 only)
+    if (r.fmt != AM_FMT_CF32 && !am_fe4_reads_raw(spc)) return hipErrorInvalidValue;
     if (am_fe4_steps(r.out_n, spc) == 0) { *layout = am_fe_plan(spc, r.out_n, 1, false); return hipSuccess; }   // nothing to launch
     switch (spc) {
-    case 1: return fe4_launch<1, 24, 2>(r, layout, s, wgs_per_cu);
-    case 2: return fe4_launch<2, 16, 2>(r, layout, s, wgs_per_cu);
-    case 4: return fe4_launch<4, 8, 2>(r, layout, s, wgs_per_cu);
-    case 5: return fe4_launch<5, 6, 2>(r, layout, s, wgs_per_cu);
-    case 8: return fe4_launch<8, 4, 2>(r, layout, s, wgs_per_cu);
-    case 10: return fe4_launch<10, 3, 2>(r, layout, s, wgs_per_cu);
-    case 16: return fe4_launch<16, 2, 2>(r, layout, s, wgs_per_cu);
-    case 20: return fe4_launch<20, 1, 2>(r, layout, s, wgs_per_cu);
+    case 1: return fe4_launch_fmt<1, 24, 2>(r, layout, s, wgs_per_cu);
+    case 2: return fe4_launch_fmt<2, 16, 2>(r, layout, s, wgs_per_cu);
+    case 4: return fe4_launch_fmt<4, 8, 2>(r, layout, s, wgs_per_cu);
+    case 5: return fe4_launch_fmt<5, 6, 2>(r, layout, s, wgs_per_cu);
+    case 8: return fe4_launch_fmt<8, 4, 2>(r, layout, s, wgs_per_cu);
+    case 10: return fe4_launch_fmt<10, 3, 2>(r, layout, s, wgs_per_cu);
+    case 16: return fe4_launch_fmt<16, 2, 2>(r, layout, s, wgs_per_cu);
+    case 20: return fe4_launch_fmt<20, 1, 2>(r, layout, s, wgs_per_cu);
 #if defined(FE4_64MSPS)
     default: return fe4_launch<32, 1, FE4_NW64>(r, layout, s, wgs_per_cu);
 #else

@@ -167,6 +167,7 @@ unsigned am_fe4_tile(int spc);              /* positions per step               
 unsigned am_fe4_lag(int spc);
 unsigned am_fe4_steps(long long out_n, int spc);
 int am_fe4_uses_fe3(int spc);               /* am_launch_fe4 runs am_k_fe3<FMT> at this rate (64 Msps, product configuration) */
+int am_fe4_reads_raw(int spc);              /* am_launch_fe4 runs am_k_fe4<SPC, G, NW, FMT> at this rate (2 .. 40 Msps) */
 unsigned am_fe3_waves(void);                /* am_k_fe3's segments (48 chips = 48 bitmap words each) per step   */
 
 /* The bitmap a streaming front end leaves and who made which part of it: workgroup g took a contiguous run of steps and formed
@@ -198,7 +199,7 @@ am_fe_layout am_fe_plan(int spc, long long out_n, unsigned resident, bool levell
 
 /* what a streaming front end is launched for (the fields am_fe3_args / am_fe4_args describe) */
 struct am_fe_stream_req {
-    const void *iq;                       /* samples of format fmt: am_k_fe3<FMT> reads them as they are; am_k_fe4: AM_FMT_CF32 only */
+    const void *iq;                       /* samples of format fmt: am_k_fe3<FMT> and am_k_fe4<..., FMT> read them as they are */
     int fmt;
     long long src_abs0, src_abs1, out_abs0, out_n;
     float *bb_sparse, *avg_sparse;        /* (bb_sparse null: am_k_fe3 writes no rows)                       */
@@ -419,7 +420,7 @@ hipError_t am_launch_extract_slice(const am_records &r, const am_dense_src &src,
 /* the same when bb exists only around the candidates: the burst is recomputed from IQ (iq[0] = absolute sample src_abs0) */
 struct am_iq_src {
     const void *iq;
-    int fmt;                   /* AM_FMT_* of iq; other than AM_FMT_CF32 at 32 samples per chip only (am_k_extract_slice_iq<32, ..., 1>) */
+    int fmt;                   /* AM_FMT_* of iq; other than AM_FMT_CF32: am_k_extract_slice_iq<SPC, ..., 1> */
     long long src_abs0, src_abs1;
     int use_pmf;
     float s1;

@@ -2530,7 +2530,9 @@ __device__ __forceinline__ float am_mag_guarded(const float2 *__restrict__ iq2, 
 
 // soft chip c of the burst whose first sample has absolute index ae (bb; the reference level comes off later).
 // inside (uniform): every lane's 16-byte loads lie inside the source -- all but the hits at the two ends of the stream
-// (RAW: never `inside` -- at 32 samples per chip, the only rate with raw samples, those hits go through am_stage_energies32)
+// (RAW: `inside` means the same of the 8- or 4-byte pair loads: the first pair starts at or behind sample ae - SPC, the last one
+// ends at or before sample ae + 239 SPC + 2, so the caller's condition covers the half pair a stream of odd length ends in.  At 32
+// samples per chip those hits go through am_stage_energies32 instead.)
 template <int SPC, int RAW = 0>
 __device__ __forceinline__ float am_soft_chip_iq(const float *__restrict__ iq, long long src_abs0, long long src_abs1,
                                                  bool pmf, float s1, long long ae, int c, bool inside, int fmt = 0)
@@ -2540,6 +2542,36 @@ __device__ __forceinline__ float am_soft_chip_iq(const float *__restrict__ iq, l
     if constexpr (RAW != 0) {
         if (!pmf) return am_mag_guarded<1>(iq2, src_abs0, src_abs1, n, fmt);
         const int ii = (int)(ae % SPC);
+        if (SPC != 32 && inside) {
+            // the float path's form below: M[k] = |.|^2 of sample w0 + k from SPC / 2 + 1 pair loads (the source is aligned to a
+            // pair and every pair lies wholly inside it: the caller's `inside`), the odd-offset select, the same order of sums
+            const long long wfirst = n - (SPC - 1);
+            const int odd = (int)((wfirst - src_abs0) & 1);
+            const long long p0 = (wfirst - odd - src_abs0) >> 1;
+            raw_pair_bits t[SPC / 2 + 1];
+#pragma unroll
+            for (int k = 0; k < SPC / 2 + 1; ++k) t[k] = raw_pair_load_rt(fmt, iq, p0 + k);
+            float M[SPC + 2];
+#pragma unroll
+            for (int k = 0; k < SPC / 2 + 1; ++k) {
+                const float2 mk = raw_pair_mag2_rt(fmt, t[k]);
+                M[2 * k] = mk.x;
+                M[2 * k + 1] = mk.y;
+            }
+            float m[SPC];
+            const uint32_t omask = 0u - (uint32_t)odd;
+#pragma unroll
+            for (int w = 0; w < SPC; ++w)
+                m[w] = __uint_as_float((__float_as_uint(M[w + 1]) & omask) | (__float_as_uint(M[w]) & ~omask));
+            const int wb = SPC - 1 - ii;
+            float pre = 0.0f, suf = 0.0f;
+#pragma unroll
+            for (int w = 0; w < SPC; ++w) {
+                if (w >= wb) pre = pre + m[w];                                // (uniform conditions)
+                if (SPC - 1 - w < wb) suf = suf + m[SPC - 1 - w];
+            }
+            return (ii == SPC - 1) ? pre * s1 : (suf + pre) * s1;             // (inside: n < src_abs1)
+        }
         float pre = 0.0f, suf = 0.0f;
 #pragma unroll 1
         for (long long w = n - ii; w <= n; ++w) pre = pre + am_mag_guarded<1>(iq2, src_abs0, src_abs1, w, fmt);
@@ -2687,7 +2719,7 @@ __device__ __forceinline__ float am_soft_chip_row32(const float *E, int row, int
 #ifndef AM_XS_WPS
 #define AM_XS_WPS 8                       /* waves per SIMD the extraction kernel is compiled for (64 VGPRs, no spills: eight workgroups per CU, 2 048 hits in flight) */
 #endif
-// RAW = 1 (32 samples per chip only): the source holds raw samples whose format comes in bits 8.. of use_pmf -- a run-time value, the
+// RAW = 1: the source holds raw samples whose format comes in bits 8.. of use_pmf -- a run-time value, the
 // same in every lane, so that the instantiations are not multiplied by the formats; RAW = 0 is the kernel as it was before.
 template <int SPC, int FIX, int GATE, int LF, int RAW>
 __global__ void __launch_bounds__(256, AM_XS_WPS)
@@ -2810,7 +2842,7 @@ hipError_t am_launch_extract_slice_iq(const am_records &r, const am_iq_src &src,
     (void)hipGetDevice(&dev);
     const int use_pmf = src.spc == 1 ? 0 : src.use_pmf;       // (a one-sample window is the sample itself: s1 = 1)
     const bool raw = src.fmt != AM_FMT_CF32;
-    if (raw && (src.spc != 32 || am_sample_bytes(src.fmt) == 0)) return hipErrorInvalidValue;      // (no such instantiation)
+    if (raw && am_sample_bytes(src.fmt) == 0) return hipErrorInvalidValue;
     const bool known = am_with_spc(src.spc, [&](auto spc) {
         am_with_fix_gate_long(o.fix_bits, o.gate, o.long_mask, [&](auto fix, auto gate, auto lf) {
             constexpr int S = decltype(spc)::value, F = decltype(fix)::value, G = decltype(gate)::value, L = decltype(lf)::value;
@@ -2833,10 +2865,8 @@ hipError_t am_launch_extract_slice_iq(const am_records &r, const am_iq_src &src,
                                src.s1, r.inavg, emit_idx, o.n_ptr, r.pos, r.e, st.base_abs, st.rate, st.tt, st.ntt, o.bursts_out,
                                o.tags_out, o.crc_pow, o.packets, o.scalars, o.host_out, o.Mp);
             };
-            if constexpr (S == 32) {
-                if (raw) { launch(std::integral_constant<int, 1>{}); return; }
-            }
-            launch(std::integral_constant<int, 0>{});
+            if (raw) launch(std::integral_constant<int, 1>{});
+            else launch(std::integral_constant<int, 0>{});
         });
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;

@@ -1,6 +1,6 @@
 // am_raw_iq.h -- native sample formats on the device: raw integer I,Q -> float32 I,Q, for the kernel that widens a whole stream
-// (am_k_unpack, am_resample.hip) and for the 64 Msps kernels that read raw samples themselves (am_k_fe3<FMT>, am_k_refine_seg<PMF, FMT>,
-// am_k_extract_slice_iq<..., 1>).  Not part of the public ABI.  DEFINITION: air_modes/formats.py
+// (am_k_unpack, am_resample.hip) and for the kernels that read raw samples themselves (64 Msps: am_k_fe3<FMT>, am_k_refine_seg<PMF, FMT>;
+// 2 .. 40 Msps: am_k_fe4<SPC, G, NW, FMT>; both: am_k_extract_slice_iq<..., 1>).  Not part of the public ABI.  DEFINITION: air_modes/formats.py
 //
 //   sc16  float(x) * 2^-15        cs8  float(x) * 2^-7        cu8  (float(x) - 127.5f) * 2^-7
 //

@@ -645,7 +645,16 @@ AM_API int am_process_samples(am_ctx *ctx, const void *raw, uint64_t n_complex, 
  * switch is the A/B lever, not a user option: default 1; it survives am_reset and am_set_rate; a new value takes effect when
  * the next stream starts (after am_create, am_reset, am_set_rate or AM_F_FLUSH).  Every other configuration -- other rates,
  * the DC blocker, am_submit_iq, pipes, K streams, shards -- widens first, whatever the switch says; so does the rest of a
- * stream whose calls change format. */
+ * stream whose calls change format.
+ * The switch has a second level.  AM_RAW_FE_ALL adds the rates am_k_fe4 serves: am_k_fe4<SPC, G, NW, FMT> stages the integers and
+ * am_k_extract_slice_iq<SPC, ..., 1> reads them; fractional rates, the DC blocker and the calls named above still widen first.
+ * am_set_raw_front_end stores 2 for 2 and 1 for every other non-zero value; am_get_raw_front_end returns the stored level.
+ * Level 2 is opt-in: it becomes the default only in a later change that edits tests/rawfe_common.py::check_route (which pins
+ * that the default widens a 20 Msps stream) and that brings the hardware measurement DESIGN.md 12 asks for. */
+#define AM_RAW_FE_OFF 0   /* widen first, everywhere                                             */
+#define AM_RAW_FE_64  1   /* default, as today: native at 64 Msps only                           */
+#define AM_RAW_FE_ALL 2   /* native at every rate the streaming front ends serve:                */
+                          /* 2, 4, 8, 10, 16, 20, 32, 40 and 64 Msps                             */
 AM_API int am_set_raw_front_end(am_ctx *ctx, int on);
 AM_API int am_get_raw_front_end(const am_ctx *ctx);
 /* Diagnostic: the AM_FMT_* the front end of the last scan read -- AM_FMT_CF32 for float32 input and for a raw stream that was

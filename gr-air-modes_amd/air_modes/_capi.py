@@ -139,6 +139,8 @@ class Library(object):
         L.am_last_num_candidates.restype = C.c_longlong
         L.am_last_num_candidates.argtypes = [vp]
         L.am_set_stream.argtypes = [vp, vp]
+        L.am_get_stream.restype = vp
+        L.am_get_stream.argtypes = [vp]
         L.am_wait_for_stream.argtypes = [vp, vp]
         L.am_signal_stream.argtypes = [vp, vp]
         L.am_shard_scan_async.argtypes = [vp, vp, u64, u64, u64, u32, vp, u64]
@@ -396,6 +398,10 @@ class Context(_DecodeOptions, _DecodeStats):
         """Device work of this context goes to the caller's HIP stream (raw handle, e.g.
         torch.cuda.current_stream().cuda_stream); None / 0: the context's own stream again."""
         self._chk(self.lib.L.am_set_stream(self._h, C.c_void_p(int(hip_stream or 0))))
+
+    def stream(self):
+        """The HIP stream this context's device work runs on now, as a raw handle (what set_stream of another stage takes)."""
+        return int(self.lib.L.am_get_stream(self._h) or 0)
 
     def wait_for_stream(self, hip_stream):
         """The context's stream waits (on the device) for what is enqueued on hip_stream so far (0 / None: the default stream)."""

@@ -17,7 +17,9 @@ cu8 (RTL-SDR); little-endian I,Q pairs, no header.  The reference's sources wide
 Input slower than 4 Msps is resampled to 4 Msps first, as modes_radio does (python/radio.py:49-53) -- with this
 package's own polyphase interpolator (air_modes/resample.py: GNU Radio's taps are not reproducible here, so that
 stage is compared by packet recall, not bit for bit); `--no-resample` processes at the rate given, which is what
-"through rx_path directly" means for the 2 Msps capture of BASELINE.json configs[0..1].
+"through rx_path directly" means for the 2 Msps capture of BASELINE.json configs[0..1].  A raw file (sc16, cs8, cu8) is
+resampled from the raw samples: one kernel launch per chunk on the receive path's stream, no float32 copy of the input and
+no host wait between the interpolator and the scan (resample.gpu_resampler.work_device_samples).
 
 A reader thread keeps one chunk ahead of the GPU (file read and resampling of chunk k+1 run under the GPU call of
 chunk k).  Differences from modes_radio, all of them outside the demodulator: no live sources (UHD / osmocom /
@@ -72,8 +74,8 @@ def build_parser():
                     "slicer_impl.cc:140 does [default: none]")
     ap.add_argument("--raw-front-end", type=int, choices=[0, 1, 2], default=None,
                     help="sc16 / cs8 / cu8 input scanned as it is, without the float32 copy: 0 = never, 1 = at 64 Msps, "
-                    "2 = at 2, 4, 8, 10, 16, 20, 32, 40 and 64 Msps (input below 4 Msps is resampled as float32 first "
-                    "unless --no-resample) [default: the library's, 1]")
+                    "2 = at 2, 4, 8, 10, 16, 20, 32, 40 and 64 Msps (input below 4 Msps goes through the resampler first, which "
+                    "reads the raw samples itself and hands the scan float32, unless --no-resample) [default: the library's, 1]")
     ap.add_argument("-l", "--location", default=None, help="receiver position as lat,lon (enables range/bearing "
                     "and surface positions)")                                                            # modes_rx:40
     ap.add_argument("-n", "--no-print", action="store_true", help="do not print decoded reports")       # modes_rx:45
@@ -124,15 +126,17 @@ def main(argv=None, out=None):
     import threading
     from . import _capi
     nslots = 2
-    drain = resample.TAPS_PER_PHASE if resampler is not None else 0
     bps = formats.bytes_per_sample(fmt)
     raw = fmt != "cf32"
-    # a slot holds a chunk at its raw width; in front of the interpolator (float32 in, on the device) the widened chunk and
-    # its drain zeros follow the raw bytes in the slot's device twin
-    float_off = (args.chunk * bps + 15) // 16 * 16 if raw and resampler is not None else 0
-    slot_bytes = float_off + 8 * (args.chunk + drain) if float_off or not raw else args.chunk * bps
-    up = _capi.Uploader((slot_bytes + 7) // 8, nslots=nslots)
-    drain_zeros = np.zeros(drain, np.complex64)
+    # a cf32 file in front of the interpolator carries its drain zeros in the slot; a raw file does not (a raw zero byte is not
+    # a zero sample): its last chunk is flushed by the interpolator itself
+    drain = resample.TAPS_PER_PHASE if resampler is not None and not raw else 0
+    # a slot holds a chunk at its raw width, and nothing else
+    up = _capi.Uploader((args.chunk * bps + 7) // 8 + drain, nslots=nslots)
+    if raw and resampler is not None:
+        # the interpolator reads the raw samples where they lie (one launch, no float32 copy) on the receive path's stream:
+        # the scan behind it is ordered by the stream, nothing waits on the host between the two
+        resampler.set_stream(rx.context().stream())
     ready = _queue.Queue()                    # (slot, samples, last) in stream order, or an exception
     free = _queue.Queue()
     for k in range(nslots):
@@ -149,7 +153,7 @@ def main(argv=None, out=None):
                     n = got // bps                                    # whole complex samples
                     last = got < want
                     if raw:
-                        up.start_bytes(slot, n * bps)                 # (raw zero bytes are not zero samples: the drain comes later)
+                        up.start_bytes(slot, n * bps)
                     else:
                         if last and drain:
                             # drain: the interpolator holds its last outputs back until it has seen what follows them
@@ -170,14 +174,7 @@ def main(argv=None, out=None):
             raise slot
         ptr = up.wait(slot)
         if raw and resampler is not None:
-            # widen behind the raw bytes, append the drain zeros as float32, then as for a cf32 file
-            ctx, fptr = rx.context(), ptr + float_off
-            ctx.unpack(ptr, fmt, fptr, n_complex=n)
-            if last:
-                ctx.unpack(drain_zeros, "cf32", fptr + 8 * n)
-                n += drain
-            ctx.synchronize()                                         # (the interpolator runs on a stream of its own)
-            ptr, n = resampler.work_device_in(fptr, n)
+            ptr, n = resampler.work_device_samples(ptr, n, fmt, flush=last)   # (python/radio.py:49-53) from the raw samples
             rx.work_device(ptr, n, flush=last)
         else:
             if resampler is not None:
@@ -201,6 +198,8 @@ def main(argv=None, out=None):
             break
     th.join()
     up.close()
+    if resampler is not None:
+        resampler.close()                     # (before the receive path whose stream it may run on)
     print("%d samples, %d packets" % (rx.samples, rx.packets), file=sys.stderr)
     return 0
 

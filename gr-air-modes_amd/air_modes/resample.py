@@ -18,6 +18,11 @@ output sample m taken at input time m / ratio from the two neighbouring
 phases with linear interpolation between them (what pfb.arb_resampler does with its derivative filter, to
 first order).  Unity DC gain.  Streaming: the last taps-per-phase input samples and the fractional read
 position are carried from one call to the next, so chunking does not change the output.
+
+Raw input (sc16, cs8, cu8: air_modes/formats.py) has an entry of its own, `work_samples`: the samples of a raw stream are those
+of the float32 stream formats.to_cf32 makes of it, and the end of a stream is a flag (eight zero samples follow in the same
+call) because a raw zero byte is not a zero sample.  On the GPU that entry is one kernel launch per call which reads the raw
+samples where they lie (am_resampler_work_samples).
 """
 import numpy as np
 
@@ -93,11 +98,34 @@ class arb_resampler(object):
         self._hist = buf[-T:]
         return y
 
+    def reset(self):
+        """A new stream starts with the next call: read position 0, no carried samples (am_resampler_reset)."""
+        self._hist = np.zeros(TAPS_PER_PHASE, np.complex128)
+        self._pos = 0.0
+
+    def work_samples(self, raw, fmt=None, flush=False):
+        """work() for a radio's native samples (air_modes/formats.py: int16 / int8 / uint8 components, I,Q interleaved; float32 /
+        complex64 is cf32): the samples of a raw stream are those of the float32 stream formats.to_cf32 makes of it.
+        flush: the stream ends here -- TAPS_PER_PHASE zero SAMPLES follow in the same call (the interpolator holds its last
+        outputs back until it has seen what follows them; a raw zero byte is not a zero sample), and the next call starts a
+        new stream."""
+        from . import formats
+        x = formats.to_cf32(raw, fmt)
+        if flush:
+            x = np.concatenate([x, np.zeros(TAPS_PER_PHASE, np.complex64)])
+        y = self.work(x)
+        if flush:
+            self.reset()
+        return y
+
 
 class gpu_resampler(object):
     """arb_resampler on the GPU (csrc/am_resample.hip), bit-identical to it.  work() returns host samples;
     work_device() leaves them on the device: (device pointer to interleaved float32 I,Q, number of complex samples),
-    valid until the next call -- what rx_path.work_device / am_process_iq(AM_F_DEVICE_IN) take."""
+    valid until the next call -- what rx_path.work_device / am_process_iq(AM_F_DEVICE_IN) take.
+    work_samples() / work_device_samples() take a radio's native samples (sc16, cs8, cu8; cf32 too) as they are: one kernel
+    launch per call, no float32 copy of the input, and with device input no host wait -- the output is ordered on the
+    handle's stream (set_stream: the receive context's, so that what follows there is ordered behind it)."""
 
     def __init__(self, ratio, device=-1, lib=None):
         import ctypes as C
@@ -115,6 +143,8 @@ class gpu_resampler(object):
         L.am_resampler_device_output.argtypes = [vp]
         L.am_resampler_last_error.restype = C.c_char_p
         L.am_resampler_last_error.argtypes = [vp]
+        L.am_resampler_work_samples.argtypes = [vp, vp, u64, C.c_int, C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.am_resampler_set_stream.argtypes = [vp, vp]
         self.ratio = float(ratio)
         self.taps = design_taps()
         self.delay = (NPHASE * TAPS_PER_PHASE - 1) / (2.0 * NPHASE)
@@ -160,4 +190,37 @@ class gpu_resampler(object):
         got = self._C.c_uint64(0)
         self._chk(self.lib.L.am_resampler_work(self._h, int(dev_ptr) if n_complex else None, int(n_complex),
                                                self._capi.AM_F_DEVICE_IN, None, 0, self._C.byref(got)))
+        return int(self.lib.L.am_resampler_device_output(self._h) or 0), int(got.value)
+
+    def reset(self):
+        """A new stream starts with the next call (am_resampler_reset)."""
+        self._chk(self.lib.L.am_resampler_reset(self._h))
+
+    def set_stream(self, hip_stream):
+        """Device work of this resampler goes to the caller's HIP stream (raw handle, e.g. Context.stream());
+        None / 0: the resampler's own stream again."""
+        self._chk(self.lib.L.am_resampler_set_stream(self._h, self._C.c_void_p(int(hip_stream or 0))))
+
+    def work_samples(self, raw, fmt=None, flush=False):
+        """arb_resampler.work_samples on the GPU: host samples in a native format (fmt: its name, None = from the dtype) ->
+        host samples.  flush: the stream ends with this call."""
+        from . import formats
+        a, name = formats.raw_components(raw, fmt)
+        n = a.size // 2
+        flags = self._capi.AM_F_FLUSH if flush else 0
+        out = np.zeros(int((n + TAPS_PER_PHASE) * self.ratio) + 16, np.complex64)
+        got = self._C.c_uint64(0)
+        self._chk(self.lib.L.am_resampler_work_samples(self._h, a.ctypes.data if n else None, n, formats.code(name), flags,
+                                                       out.ctypes.data, out.size, self._C.byref(got)))
+        return out[:int(got.value)].copy()
+
+    def work_device_samples(self, dev_ptr, n_complex, fmt, flush=False):
+        """The same with the raw samples already in this GPU's memory (aligned to a component) and the output left there:
+        (device pointer, number of complex samples), valid until the next call.  Returns without waiting for the device: the
+        output is ordered on the resampler's stream (set_stream)."""
+        from . import formats
+        flags = self._capi.AM_F_DEVICE_IN | (self._capi.AM_F_FLUSH if flush else 0)
+        got = self._C.c_uint64(0)
+        self._chk(self.lib.L.am_resampler_work_samples(self._h, int(dev_ptr) if n_complex else None, int(n_complex),
+                                                       formats.code(fmt), flags, None, 0, self._C.byref(got)))
         return int(self.lib.L.am_resampler_device_output(self._h) or 0), int(got.value)

@@ -1394,6 +1394,8 @@ int am_set_stream(am_ctx *c, void *hip_stream)
     return AM_OK;
 }
 
+void *am_get_stream(const am_ctx *c) { return c ? (void *)c->stream : nullptr; }
+
 // Order the context's stream behind everything enqueued so far on another stream of the same device (hip_stream = NULL:
 // the legacy default stream, which is PyTorch's "current stream" unless the caller changed it): an event recorded
 // there, waited for here; the host does not block.  For inputs produced by somebody else's stream (an RCCL receive).

@@ -372,6 +372,10 @@ AM_API int am_spipe_get_address_repair_stats(const am_spipe *pipe, uint64_t *rep
  * synchronisation.  The stream must outlive the context or be replaced before it is destroyed.  (No counterpart in
  * the reference: GNU Radio blocks have no device streams.) */
 AM_API int am_set_stream(am_ctx *ctx, void *hip_stream);
+/* The stream the context's device work runs on now (its own, or the one am_set_stream gave it), as a hipStream_t: for
+ * stages that feed the context and want to be ordered in front of it without an event, e.g. am_resampler_set_stream.
+ * NULL on a null context. */
+AM_API void *am_get_stream(const am_ctx *ctx);
 /* Order the context's stream behind everything enqueued so far on another stream of the same device (NULL = the legacy
  * default stream, PyTorch's current stream unless the caller changed it): an event recorded there and waited for here,
  * the host does not block.  For inputs another stream produces -- e.g. boundary samples an RCCL receive is still
@@ -583,6 +587,28 @@ AM_API int am_resampler_work(am_resampler *h, const float *iq, uint64_t n_comple
                       uint64_t *n_out);
 AM_API const float *am_resampler_device_output(const am_resampler *h);
 AM_API const char *am_resampler_last_error(const am_resampler *h);
+/* The same stage for a radio's native samples (python/radio.py:164-231's sources in front of python/radio.py:49-53's
+ * resampler), in ONE kernel launch per call and without a float32 copy of the input: the kernel reads the AM_FMT_* samples
+ * (declared below) where they lie and widens them as am_unpack would.  DEFINITION: arb_resampler.work_samples of
+ * air_modes/resample.py -- the outputs are am_resampler_work's on am_unpack's output, bit for bit, whatever the chunking.
+ *   raw        n_complex samples of format fmt: host memory, or device memory with AM_F_DEVICE_IN; aligned to a component.
+ *   AM_F_FLUSH the stream ends with this call: eight zero SAMPLES follow the call's own in the same call (the drain: the
+ *              interpolator holds its last outputs back until it has seen what follows them), then position and carried samples
+ *              are cleared as by am_resampler_reset.  With n_complex == 0 it drains only.
+ *   out / cap / AM_F_DEVICE_OUT / am_resampler_device_output as for am_resampler_work.  *n_out is computed on the host before
+ *              anything runs and is always written (AM_ECAPACITY: the count needed; the output is in the handle's buffer).
+ * With AM_F_DEVICE_IN and (out == NULL or AM_F_DEVICE_OUT) the call returns WITHOUT waiting: the output is ordered on the
+ * handle's stream.  With host input it returns once the raw bytes have left the caller's buffer, with host output when the
+ * output is there.  AM_EINVAL for an unknown format, a null pointer with n_complex > 0, and n_complex > 2^31.
+ * AM_FMT_CF32 gives am_resampler_work's result.  Calls of both kinds may be mixed on one handle: they carry one state.
+ * am_resampler_work itself still returns only when its output is complete. */
+AM_API int am_resampler_work_samples(am_resampler *h, const void *raw, uint64_t n_complex, int fmt, uint32_t flags, float *out,
+                                     uint64_t cap, uint64_t *n_out);
+/* Run the handle's device work on the caller's HIP stream (NULL: back to the handle's own), as am_set_stream does for a
+ * context.  On the receive context's stream (am_get_stream) the am_process_iq(..., AM_F_DEVICE_IN) behind an
+ * am_resampler_work_samples call is ordered by the stream, and nothing waits on the host between python/radio.py:49-53's
+ * resampler and rx_path.  The stream must outlive the handle or be replaced before it is destroyed. */
+AM_API int am_resampler_set_stream(am_resampler *h, void *hip_stream);
 
 /* ---- pinned staging for a host source (apps/modes_rx's file source, python/radio.py:221-234) --------------------
  * nslots pinned host buffers of capacity_complex samples each, with a device twin and a copy stream: the reader fills
